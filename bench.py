@@ -140,6 +140,26 @@ def cpu_baseline_evo(cands, seconds_budget=20.0):
                       "torch %d threads" % (n, B, cores)}
 
 
+DUMP_SAMPLE = 1 << 22                            # elements kept of an output larger than this (16 MB of float32 per array)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor} as <path>/<name>.npy in float32.  An array of more than DUMP_SAMPLE elements is reduced
+    to a fixed sample (sorted indices drawn with seed 0 from its flattened length), so two builds compare element for element."""
+    import numpy as np
+    fresh = not os.path.isdir(path) or not os.listdir(path)
+    os.makedirs(path, exist_ok=True)
+    if fresh:                                    # a directory of outputs only: keep it out of version control wherever it lies
+        with open(os.path.join(path, ".gitignore"), "w") as f:
+            f.write("*\n")
+    for name, v in arrays.items():
+        v = v.detach().float()
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_SAMPLE, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        np.save(os.path.join(path, name + ".npy"), v.cpu().numpy())
+
+
 def write_launch_table(path, profile, descs, steps):
     rows = {}
     for (kind, fl, dense, by, e0, e1), desc in zip(profile, descs):
@@ -179,6 +199,7 @@ def run_evo_eval(args, rank, world, device):
     x = torch.randn(B, 3, 224, 224, generator=g).to(device)
     y = torch.randint(0, 1000, (B,), generator=g).to(device)
     plans = {}
+    last = {}
 
     def step(i):
         ci = mine[i % len(mine)]
@@ -187,7 +208,10 @@ def run_evo_eval(args, rank, world, device):
         with torch.no_grad():
             out = model(x, plan=plans[ci])
         out = out[0] if isinstance(out, tuple) else out
-        return (out.argmax(dim=1) == y).sum()
+        hits = (out.argmax(dim=1) == y).sum()
+        if args.dump_outputs:
+            last["logits"], last["hits"] = out, hits
+        return hits
     step_probe = [] if os.environ.get("VITRES_DBG_STEPS") else None   # dev aid: GPU time of every step from the first warm-up step on
     if step_probe is not None:
         _step = step
@@ -217,6 +241,8 @@ def run_evo_eval(args, rank, world, device):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     elapsed = float(tmax.item())
     assert all(0 <= int(h) <= B for h in hits)
+    if args.dump_outputs and rank == 0:              # the last timed candidate's logits and hit count, before the profiled steps
+        dump_outputs(args.dump_outputs, last)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -300,6 +326,10 @@ def main():
     ap.add_argument("--wire", default="f32", choices=["f32", "bf16"], help="dtype of the gradients on the wire (N > 1): bf16 halves "
                     "the bytes of the exchange (engine.GradSync(wire_dtype=torch.bfloat16)); the default is the reference's fp32")
     ap.add_argument("--no-graph", action="store_true", help="issue every kernel from Python instead of replaying a hipGraph")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last one returned "
+                    "(rank 0) as DIR/<name>.npy, float32: training workloads loss; evo_eval_sr_small logits and hits.  Arrays of more "
+                    "than 4M elements are a fixed seeded sample.  Inputs, weights and sampled sub-networks are seeded: the same "
+                    "arguments give the same inputs")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -448,6 +478,12 @@ def main():
     elapsed = float(tmax.item())
     lossv = torch.stack(losses).tolist()
     assert all(v == v and abs(v) != float("inf") for v in lossv), "non-finite loss"
+    if args.dump_outputs and rank == 0:
+        # what a caller of the training step receives: the last timed step's loss.  The weights and gradients it leaves in the arena
+        # are not stable from run to run: the weight-gradient kernels accumulate fp32 partial sums with atomics (summation order
+        # varies), the next bf16 step turns that into bf16-ulp differences, and AdamW turns sign changes of near-zero gradients into
+        # whole learning-rate steps -- the same build differs by up to 50 % on single bias elements after two steps
+        dump_outputs(args.dump_outputs, {"loss": losses[-1]})
     if step_probe:
         print("step probe (ms, from the first warm-up step): " + " ".join("%.2f" % a.elapsed_time(b) for a, b in step_probe),
               file=sys.stderr)

@@ -3,6 +3,11 @@ import sys
 
 import pytest
 
+# torch's CPU erfinv (trunc_normal_ initialisation) goes through MKL, whose default code path differs between Intel and AMD CPUs
+# in the last bits; the bit-exact initialisation goldens (F12, F16) hold on both only in MKL's SSE2 path, which AMD CPUs always
+# take.  Set before torch (and MKL) is loaded; tests/golden/make_golden.py pins the same path.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, "vit-search_amd"), os.path.join(ROOT, "tests", "golden"), os.path.join(ROOT, "oracle")):
     if p not in sys.path:

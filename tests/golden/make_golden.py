@@ -13,7 +13,10 @@ import sys
 import warnings
 
 import numpy as np
-import torch
+
+# MKL's SSE2 code path, as in tests/conftest.py: the bit-exact initialisation vectors (F12, F16) then hold on Intel and AMD CPUs
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+import torch  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
