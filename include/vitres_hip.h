@@ -10,7 +10,9 @@
  * Conventions (all entry points):
  *   - extern "C", plain device pointers and sizes; no torch types.
  *   - The caller owns every buffer (inputs, outputs, workspaces); the library never allocates,
- *     frees or retains pointers and keeps no global mutable state; re-entrant.
+ *     frees or retains pointers; re-entrant.  Its only mutable state is a few function-local
+ *     caches of device facts, filled on first use: the CU count (gemm.hip) and the dynamic-LDS
+ *     limit already granted to each attention kernel (attn.hip, attn_mfma.hip).
  *   - All work is enqueued asynchronously on `stream`; no hidden synchronisation.
  *   - Return value: 0 = ok; > 0 = hipError_t of the launch; < 0 = argument validation
  *     (VR_EINVAL -1, VR_EALIGN -2, VR_EUNSUPPORTED -3).  No exceptions cross the ABI.
@@ -108,6 +110,9 @@ typedef struct vr_gemm_args {
                                 workgroup per CU, one token split for the whole group (faster alone, +0.05 ms inside the step: opt-in);
                             128 (vr_gemm_group, first problem) = the group may fill the chip (default: at most two resident
                                 workgroups per CU);
+                            0x2000 / 0x4000 (vr_gemm_group weight-gradient problems) = measurement aids that produce WRONG results:
+                                the problem skips its epilogue / its K loop; a group whose first problem carries either bit runs on
+                                tn_body's group kernel (as with 64);
                             0x100 = gemm_nt.hip's kernels instead of the lean-loop ones (gemm_ntk.hip);
                             0x600 / 0x1800 = slice buffers (1 - 3; see `ring`) / tile (1: 128 x 128, 2: 64 x 128, 3: 64 x 64) of the
                                 lean-loop kernels instead of their grid-size rule (tests);

@@ -313,7 +313,7 @@ def test_masked_tiles_left_unwritten_are_never_read(case, monkeypatch):
     out = {}
     for mode in ("write", "write again", "skip", "skip+poison"):
         monkeypatch.setattr(V, "_SKIP_WRITES", not mode.startswith("write"))
-        monkeypatch.setattr(K, "DBG_POISON", [mode == "skip+poison"])
+        monkeypatch.setattr(K, "DBG_POISON", mode == "skip+poison")
         res = []
         if case.endswith("graph"):
             from vitres import engine
@@ -444,7 +444,7 @@ def test_benched_configuration_vs_cpu_oracle(space, B, epa, dp):
 
 
 def test_full_size_ln_fold_equals_separate_kernels(monkeypatch):
-    """Round 6: vr_gemm_ln_fold inside the model (opt-in, VITRES_LN_FOLD): the sr_tiny supernet at B = 16 with the LayerNorm of stages
+    """Round 6: vr_gemm_ln_fold inside the model (opt-in, kernels.LN_FOLD): the sr_tiny supernet at B = 16 with the LayerNorm of stages
     2 - 3 folded into its producer gives the forward of the default path bit for bit (same GEMM kernel, same row routine) and the
     same gradients up to the order of the fp32 atomics."""
     from vitres import kernels as K

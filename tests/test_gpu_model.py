@@ -478,8 +478,8 @@ def test_model_at_280px_uses_long_attention():
 
 @pytest.mark.gpu
 def test_fused_layernorm_kernels_match_separate_kernels(monkeypatch):
-    """functional.FUSE_LN=3 (opt-in vr_gemm_ln: LayerNorm forward / backward in the epilogue of the neighbouring Linear) gives
-    the logits and gradients of the default vr_gemm + vr_ln_fwd / vr_ln_bwd sequence within bf16 rounding."""
+    """functional.FUSE_LN (vr_gemm_ln: LayerNorm forward / backward in the epilogue of the neighbouring Linear) gives the logits
+    and gradients of the separate vr_gemm + vr_ln_fwd / vr_ln_bwd sequence (FUSE_LN = False) within bf16 rounding."""
     import vitres.functional as Fn
     from vitres.losses import SoftTargetCrossEntropy
     prod, orc, sd = build_pair(0, "multi", 100)
@@ -500,8 +500,8 @@ def test_fused_layernorm_kernels_match_separate_kernels(monkeypatch):
         loss.backward()
         torch.cuda.synchronize()
         return out[0].detach().float().cpu(), {n: p.grad.detach().float().cpu().clone() for n, p in prod.named_parameters()}
-    c0, g0 = run(0)
-    c3, g3 = run(3)
+    c0, g0 = run(False)
+    c3, g3 = run(True)
     assert rel(c3, c0) < 2e-2
     worst = max(rel(g3[n], g0[n]) for n in g0 if float(g0[n].abs().max()) > 0)
     assert worst < 6e-2, worst
@@ -747,35 +747,19 @@ def test_single_stage_patch16_sibling_vs_reference_golden(mode, dtype):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dtype,defer", [(torch.float32, "0"), (torch.bfloat16, "0"), (torch.bfloat16, "1"), (torch.float32, "1"),
-                                         (torch.bfloat16, "overlap1"), (torch.bfloat16, "overlap2"), (torch.float32, "overlap2"),
-                                         (torch.float32, "overlap2s2"), (torch.bfloat16, "overlap2s2"),
-                                         (torch.bfloat16, "1+overlap1")])
-def test_optimizer_inside_the_graph_equals_step_after_the_graph(dtype, defer, monkeypatch):
+@pytest.mark.parametrize("dtype,overlap", [(torch.float32, 0), (torch.bfloat16, 0), (torch.bfloat16, 1), (torch.bfloat16, 2),
+                                           (torch.float32, 2)],
+                         ids=["dtype0-0", "dtype1-0", "dtype4-overlap1", "dtype5-overlap2", "dtype6-overlap2"])
+# (ids: those the cases had before the deferred-update and two-side-stream cases were deleted with their code)
+def test_optimizer_inside_the_graph_equals_step_after_the_graph(dtype, overlap):
     """GraphedTrainStep(optimizer=FlatAdamW): the AdamW update captured into the step's hipGraph (hyper-parameters read from device
     memory that prepare_step() rewrites per step) walks the same parameter trajectory as graph replay + optimizer.step(),
-    including a learning-rate change between steps.  defer = 1: the graph OPENS with the previous replay's update (arena head on
-    the main stream, the rest beside the first stage's forward), the first replay's update is a no-op and finish_update() applies
-    the last one."""
+    including a learning-rate change between steps."""
     from vitres import engine
     from vitres.optim import FlatAdamW
     from vitres.losses import SoftTargetCrossEntropy
-    # overlapN (round 4): the N ranges at the arena's end are updated on the weight gradients' stream as soon as the backward
+    # overlap = N > 0 (round 4): the N ranges at the arena's end are updated on the weight gradients' stream as soon as the backward
     # part that completes them is through, by a capped launch, beside the rest of the backward
-    # ...s2 (ADVICE round 4): two side streams -- the weight-gradient groups go round-robin over them, the early update has to be
-    # ordered behind BOTH (functional.on_side(after_all_sides=True))
-    from vitres import functional as Fn
-    if defer.endswith("s2"):
-        defer = defer[:-2]
-        monkeypatch.setattr(Fn, "N_SIDE", 2)
-        monkeypatch.setattr(Fn, "_side_streams", {})
-    # 1+overlap1 (round 5): VITRES_OPT_DEFER=1 with the DEFAULT overlap setting -- the early-update cut used to stay armed and left
-    # the capture with unjoined side work
-    overlap = "1" if defer == "1+overlap1" else (defer[len("overlap"):] if defer.startswith("overlap") else "0")
-    defer = "1" if defer == "1+overlap1" else ("0" if defer.startswith("overlap") else defer)
-    monkeypatch.setenv("VITRES_OPT_DEFER", defer)
-    monkeypatch.setenv("VITRES_OPT_OVERLAP", overlap)
-    monkeypatch.setenv("VITRES_OPT_OVERLAP_BLOCKS", "8")
     crit = SoftTargetCrossEntropy()
     x, t, pt, _ = (v.to(DEV) for v in recipe.inputs(7, 8, recipe.MICRO_IMG, recipe.MICRO_CLASSES, 1))
     runs = []
@@ -788,26 +772,22 @@ def test_optimizer_inside_the_graph_equals_step_after_the_graph(dtype, defer, mo
         opt = FlatAdamW(prod, engine.param_groups_weight_decay(prod, 0.05), lr=2e-3, ema_decay=0.99)
         if dtype == torch.bfloat16:
             opt.own_shadow()
-        g = engine.GraphedTrainStep(prod, crit, x, t, pt, "seq", optimizer=opt if in_graph else None)
+        g = engine.GraphedTrainStep(prod, crit, x, t, pt, "seq", optimizer=opt if in_graph else None, opt_overlap=overlap,
+                                    opt_overlap_blocks=8)
         assert (g.optimizer is not None) == in_graph
-        if in_graph:
-            assert (g.defer is not None) == (defer == "1")
+        assert g.defer is None
         losses = []
         for it in range(4):
             torch.manual_seed(900 + it)
             if it == 2:
-                if in_graph:
-                    g.finish_update()                              # (a learning-rate change: the pending update is due first)
                 for grp in opt.param_groups:
                     grp["lr"] = 5e-4                               # scheduler-style change
             if in_graph:
-                if g.defer is None:
-                    opt.prepare_step()
+                opt.prepare_step()
                 losses.append(g(x, t, pt, epoch=31, train_iter=it, arch_sample=None).item())
             else:
                 losses.append(g(x, t, pt, epoch=31, train_iter=it, arch_sample=None).item())
                 opt.step()
-        g.finish_update()
         torch.cuda.synchronize()
         runs.append((losses, prod._arena["flat"].clone(), opt._flat_state["v"].clone(), opt._flat_state["ema"].clone(), opt._step,
                      prod._arena["shadow"].clone() if dtype == torch.bfloat16 else None))
@@ -900,39 +880,55 @@ def test_bf16_step_trains_like_the_fp32_step():
     assert rel_.max() < 0.06 and rel_.mean() < 0.02, msg
 
 
-OPT_IN_FORMS = ["VITRES_EMBED_WGRAD_SLICES=0", "VITRES_OVERLAP=0", "VITRES_DBG_K_SHARES=2", "VITRES_DBG_WGRAD_SCHED=0x10000",
-                "VITRES_DBG_WGRAD_SCHED=64", "VITRES_FUSE_LN=0", "VITRES_LN_FOLD=1"]
+# (module of vitres, attribute, value): the single-stream step, the K-split GEMM form, the 8-wave and the tn_body weight-gradient
+# group kernels, the separate LayerNorm kernels, the LayerNorm folded into the tiled Linear
+OPT_IN_FORMS = [("functional", "OVERLAP", False), ("kernels", "K_SHARES", 2), ("functional", "WGRAD_SCHED", 0x10000),
+                ("functional", "WGRAD_SCHED", 64), ("functional", "FUSE_LN", False), ("kernels", "LN_FOLD", True)]
 # (the conv stem's patch-direct path is the default that test_gpu_fullsize's bf16 gradient tests hold against the reference;
 # its kernels are pinned bit for bit to the unfold / fold forms in test_stem_glue_kernels)
 
 
-def test_opt_in_forms_at_model_level(tmp_path):
-    """Every kernel form / schedule that stays in the product library behind an environment knob runs one whole bf16 training step
-    of the micro supernet (tests/knob_worker.py, one process per setting: the knobs are read at import time) and must reproduce the
-    default path: masks bit for bit, logits / loss / every parameter gradient up to fp32 summation order of bf16 products."""
-    import subprocess
-    import sys
+def _micro_bf16_step():
+    """One bf16 training step (forward + loss + backward) of a fresh micro supernet on fixed inputs: keeps, logits, loss and
+    every parameter gradient."""
+    nd = recipe.MICRO_DEFS[0]
+    kw = dict(num_channels_to_keep=recipe.micro_keep_config(), example_per_arch=2, num_warmup_epochs=30)
+    prod = vitres.create_model("flexible_vit_sr_patch14_224_patch_output_supernet", img_size=recipe.MICRO_IMG,
+                               num_classes=recipe.MICRO_CLASSES, network_def=nd, drop_path_rate=0.0, drop_block_rate=None, **kw)
+    sd = recipe.fill_state_dict([(k, tuple(v.shape)) for k, v in prod.state_dict().items()], 100)
+    prod.load_state_dict(sd)
+    prod = prod.to(DEV).set_compute_dtype(torch.bfloat16)
+    x, t, pt, _ = recipe.inputs(7, 8, recipe.MICRO_IMG, recipe.MICRO_CLASSES, 1)
+    prod.train()
+    prod.set_epoch(31)
+    torch.manual_seed(0)
+    cls, pat = prod(x.to(DEV), patch_output_type="seq")
+    loss = O.soft_target_ce(cls, t.to(DEV)) + O.soft_target_ce(pat, pt.to(DEV))
+    loss.backward()
+    torch.cuda.synchronize()
+    return {"keeps": [k.cpu() if torch.is_tensor(k) else k for k in prod.last_keeps], "cls": cls.detach().float().cpu(),
+            "pat": pat.detach().float().cpu(), "loss": float(loss),
+            "grads": {n: p.grad.detach().float().cpu() for n, p in prod.named_parameters()}}
 
-    def run(env_s, tag):
-        env = dict(os.environ)
-        for kv in env_s.split():
-            k, v = kv.split("=")
-            env[k] = v
-        out = str(tmp_path / ("%s.pt" % tag))
-        subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "knob_worker.py"), out],
-                       env=env, check=True, timeout=600)
-        return torch.load(out)
 
-    ref = run("", "default")
-    for i, env_s in enumerate(OPT_IN_FORMS):
-        got = run(env_s, "k%d" % i)
+def test_opt_in_forms_at_model_level(monkeypatch):
+    """Every kernel form / schedule that stays in the product library as an opt-in (a module attribute of vitres) runs one whole
+    bf16 training step of a fresh micro supernet and must reproduce the default path: masks bit for bit, logits / loss / every
+    parameter gradient up to fp32 summation order of bf16 products."""
+    import importlib
+    ref = _micro_bf16_step()
+    for mod, name, value in OPT_IN_FORMS:
+        form = "%s.%s=%r" % (mod, name, value)
+        with monkeypatch.context() as m:
+            m.setattr(importlib.import_module("vitres." + mod), name, value)
+            got = _micro_bf16_step()
         assert len(got["keeps"]) == len(ref["keeps"])
         for a, b in zip(got["keeps"], ref["keeps"]):
-            assert (a is None and b is None) or torch.equal(torch.as_tensor(a), torch.as_tensor(b)), env_s
-        assert rel(got["cls"], ref["cls"]) < 5e-3 and rel(got["pat"], ref["pat"]) < 5e-3, env_s
-        assert abs(got["loss"] - ref["loss"]) < 2e-3 * abs(ref["loss"]), env_s
+            assert (a is None and b is None) or torch.equal(torch.as_tensor(a), torch.as_tensor(b)), form
+        assert rel(got["cls"], ref["cls"]) < 5e-3 and rel(got["pat"], ref["pat"]) < 5e-3, form
+        assert abs(got["loss"] - ref["loss"]) < 2e-3 * abs(ref["loss"]), form
         worst = max(rel(g, ref["grads"][n]) for n, g in got["grads"].items())
-        assert worst < 2e-2, (env_s, worst)
+        assert worst < 2e-2, (form, worst)
 
 
 @pytest.mark.gpu
@@ -941,7 +937,7 @@ def test_dropped_layers_and_dropped_samples_are_skipped_exactly(dtype, monkeypat
     """Round 5: a dropped layer (layer keep 0 for an architecture group) and a DropPath-dropped sample zero the attention / MLP widths
     the KERNELS read (vit_sr_supernet.sample_plan / plan_host_buffer), so that their qkv / fc1 GEMMs, attention cores and backward are
     skipped instead of computed and multiplied by zero.  Results -- loss, logits, every parameter gradient -- must be those of the
-    computing path (VITRES_SKIP_DROPPED_LAYERS=0), and the sampled keeps reported to the caller must be untouched."""
+    computing path (_SKIP_DROPPED = False), and the sampled keeps reported to the caller must be untouched."""
     from vitres.nets import vit_sr_supernet as V
     x, t, pt, _ = (v.to(DEV) for v in recipe.inputs(7, 8, recipe.MICRO_IMG, recipe.MICRO_CLASSES, 1))
     out = {}

@@ -1,16 +1,17 @@
 #!/usr/bin/env python
 """The weight-gradient group launches of the step alone (dev tool): one vr_gemm_group per transformer block of each stage, replayed
-from a hipGraph (the host needs ~10 us per eager launch): the 4-wave kernel (sched 64 on the first problem; VITRES_DBG_TN=1 / 2:
-without the atomics / without the K loop) against the 8-wave, double-buffered one (round 6), dense and with two architecture groups
-(`--masked`: the second group keeps 5/8 of every width)."""
+from a hipGraph (the host needs ~10 us per eager launch): the 4-wave kernel (sched 64 on the first problem; `--dbg 1` / `--dbg 2`:
+sched bit 0x2000 / 0x4000 on its problems, without the epilogue / without the K loop -- wrong results) against the 8-wave,
+double-buffered one (round 6), dense and with two architecture groups (`--masked`: the second group keeps 5/8 of every width)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vit-search_amd"))
 import torch
 from vitres import kernels as K
 dev, bf = "cuda", torch.bfloat16
+dbg = int(sys.argv[sys.argv.index("--dbg") + 1]) & 3 if "--dbg" in sys.argv else 0
 tag = " ".join("%s=%s" % (k, v) for k, v in sorted(os.environ.items()) if k.startswith("VITRES_"))
-print("# " + (tag or "default"))
+print("# " + (" ".join(t for t in (tag, "dbg=%d" % dbg if dbg else "") if t) or "default"))
 for (T, C, F, HD, name) in [(32896, 256, 768, 256, "stage 1"), (8320, 512, 1536, 512, "stage 2"), (2176, 1024, 3072, 768, "stage 3")]:
     r = lambda *s: torch.randn(*s, device=dev).to(bf)
     xn, dqkv, ao, gt, xn2, du, h = r(T, C), r(T, 3 * HD), r(T, HD), r(T, C), r(T, C), r(T, F), r(T, F)
@@ -43,7 +44,7 @@ for (T, C, F, HD, name) in [(32896, 256, 768, 256, "stage 1"), (8320, 512, 1536,
     kC, kF, kH = keep(C), keep(F), keep(HD)
     xn, xn2, gt, ao, du, h, dqkv = zero_masked(xn, kC), zero_masked(xn2, kC), zero_masked(gt, kC), zero_masked(ao, kH), zero_masked(du, kF), zero_masked(h, kF), zero_masked(dqkv, kH, HD)
     res = []
-    for sched in (64, 0, 0x10000):
+    for sched in (64 | dbg << 13, 0, 0x10000):
         calls = [call(gt, h, dws[3], dbs[3], sched, kC, kF), call(du, xn2, dws[2], dbs[2], sched, kF, kC), call(gt, ao, dws[1], dbs[1], sched, kC, kH),
                  call(dqkv, xn, dws[0], dbs[0], sched, kH, kC, HD)]
         for d in dws + dbs:

@@ -20,8 +20,6 @@
 //
 // The Linear's bias gradient (column sums of dY) is one more MFMA per A fragment against an all-ones B fragment, done
 // by the workgroups of the first column tile only.
-#include <cstdlib>
-
 #include "common.h"
 #include "../../include/vitres_hip.h"
 #include "gemm_shared.h"
@@ -71,7 +69,7 @@ template <int ROWB> __device__ __forceinline__ bfv8 tr_frag(const char* p) {
 // TW: tile = TW x TW outputs.  64 for small weights: the atomic volume (split x |W|) is the same as with 128 x 128 tiles, but
 // four times as many workgroups share it -- a 768 x 256 weight is 12 tiles of 128^2, i.e. ~200 workgroups at the coarse token
 // split the atomics call for, each running its 32 slices alone on a CU at the full ~1.5 us slice latency.
-// STAGES = 3 (opt-in, VITRES_TN_STAGES=3): ring of three slice buffers, two slices in flight (counted vmcnt + raw barrier, as
+// STAGES = 3 (opt-in): ring of three slice buffers, two slices in flight (counted vmcnt + raw barrier, as
 // gemm_nt.hip).  Faster alone; inside the training step its 96 KB of LDS displace the data-gradient workgroups it runs beside
 // (measured -5 %), so the default stays the single buffer.
 template <bool BIAS, bool MAPPED, int TW, int STAGES>
@@ -126,7 +124,7 @@ __device__ __forceinline__ void tn_body(const vr_gemm_args& p, const int bid) {
     // read-modify-write; a fully masked tile must then write its zeros instead of leaving
     const bool store = p.atomic == 2;
     if (ntiles == 0 && !store) return;
-    const bool nochunk = (p.sched & 0x8000) != 0;                                // (sched 0x8000 / VITRES_DBG_TN=4: A/B aid)
+    const bool nochunk = (p.sched & 0x8000) != 0;                                // (sched 0x8000: A/B aid)
     const bool skipm = nochunk || !p.keep_k || (p.k_period > 0 && (p.k_period & 7)), skipn = nochunk || !p.keep_n || (p.n_period > 0 && (p.n_period & 7));
 
     // ---- LDS-DMA source addressing: piece h of this wave = slice tokens (wave*PPW + h)*TPP .. ; lane -> (token, slot) ----
@@ -219,7 +217,7 @@ __device__ __forceinline__ void tn_body(const vr_gemm_args& p, const int bid) {
             }
         }
     };
-    const int dbg = (p.sched >> 13) & 3;         // measurement aid (VITRES_DBG_TN; wrong results): 1 no epilogue, 2 no K loop
+    const int dbg = (p.sched >> 13) & 3;         // measurement aid (sched 0x2000 / 0x4000; wrong results): 1 no epilogue, 2 no K loop
     if (dbg == 2) ntiles = 0;
     if constexpr (STAGES == 1) {
         for (int kt = 0; kt < ntiles; ++kt) {
@@ -603,10 +601,8 @@ bool vr_gemm_tn_group_launch(const vr_gemm_args* args, int count, hipStream_t st
         work += (long long)((args[i].M + TWv - 1) / TWv) * ((args[i].N + TWv - 1) / TWv) * ((args[i].K + BT - 1) / BT);
     long long spw = work / (2LL * n_cu);
     spw = spw < 8 ? 8 : (spw > 32 ? 32 : spw);
-    static const int knob_dbg = std::getenv("VITRES_DBG_TN") ? std::atoi(std::getenv("VITRES_DBG_TN")) : 0;
     for (int i = 0; i < count; ++i) {
         g.a[i] = args[i];
-        g.a[i].sched |= (knob_dbg & 3) << 13;
         const long long sl_i = (args[i].K + BT - 1) / BT;
         const long long tiles = (long long)((args[i].M + TWv - 1) / TWv) * ((args[i].N + TWv - 1) / TWv);
         long long split = args[i].atomic == 2 ? 1 : (sl_i + spw - 1) / spw;       // store form: one workgroup per tile
@@ -621,7 +617,7 @@ bool vr_gemm_tn_group_launch(const vr_gemm_args* args, int count, hipStream_t st
         grid = next < lim ? next : lim;
     }
     if (TWv == 64) hipLaunchKernelGGL((tn_group_kernel<false, 64>), dim3((unsigned)grid), dim3(NTHR), 0, stream, g);
-    else if (any_store || knob_dbg || !lean_ok || (args[0].sched & 64)) hipLaunchKernelGGL((tn_group_kernel<false, 128>), dim3((unsigned)grid), dim3(NTHR), 0, stream, g);
+    else if (any_store || !lean_ok || (args[0].sched & (64 | 0x6000))) hipLaunchKernelGGL((tn_group_kernel<false, 128>), dim3((unsigned)grid), dim3(NTHR), 0, stream, g);
     else hipLaunchKernelGGL(tn8_group_kernel<4>, dim3((unsigned)grid), dim3(NTHR), 0, stream, g);     // (sched 64: tn_body's instruction stream, tests)
     return true;
 }

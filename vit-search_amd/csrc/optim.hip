@@ -111,7 +111,7 @@ extern "C" int vr_adamw_flat_dev(float* p, const float* g, float* m, float* v, v
 }
 
 // The same launch capped at `max_blocks` resident workgroups (grid-stride): an update of a finished arena range that runs on the
-// weight gradients' stream beside the rest of the backward must not take the chip (engine.GraphedTrainStep, VITRES_OPT_OVERLAP).
+// weight gradients' stream beside the rest of the backward must not take the chip (engine.GraphedTrainStep, opt_overlap_blocks).
 extern "C" int vr_adamw_flat_dev_capped(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_decay,
                                         const uint8_t* group_of_8, const vr_adamw_group* groups_dev, int32_t n_groups, int64_t n,
                                         int32_t max_blocks, vr_stream_t stream) {

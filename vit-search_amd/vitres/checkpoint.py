@@ -73,9 +73,6 @@ def checkpoint_dict(model, optimizer, lr_scheduler, epoch, args=None, model_ema=
             if len(rng_states) != world:
                 raise ValueError('rng_states has %d entries for %d ranks' % (len(rng_states), world))
             out['vitres_rng']['drop_path_by_rank'] = list(rng_states)
-    if getattr(optimizer, '_graph_pending', None) is not None and optimizer._graph_pending():
-        raise RuntimeError('a deferred in-graph optimizer update is pending: call GraphedTrainStep.finish_update() before '
-                           'checkpointing (the weights are one step behind)')
     return out
 
 

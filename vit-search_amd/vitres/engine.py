@@ -10,7 +10,6 @@ ranks are averaged by one flat all-reduce (GradSync) instead of DDP buckets; the
 done on the device and read back every `sync_every` iterations (reference: every iteration).
 """
 import math
-import os
 import sys
 import time
 from collections import defaultdict
@@ -271,8 +270,11 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
     return loss.detach()
 
 
-RUN_AHEAD = int(os.environ.get("VITRES_RUN_AHEAD", "2"))
-PLAN_COPY_KERNEL = os.environ.get("VITRES_PLAN_COPY", "kernel") == "kernel"     # the per-step plan buffer: kernel reading pinned memory / memcpy
+# bounded run-ahead: the host needs ~3 ms for a 7.5 ms step, so left alone it queues replay after replay until the runtime's
+# queue limit stops it (~25 steps in); on the way the runtime grows its per-launch resources a few times, and each growth
+# stalls the device for ~1 ms (six 8.3 - 8.9 ms steps among the first 26 of a run, none after).  RUN_AHEAD replays in
+# flight keep the device fed with the host two steps ahead from the third step on.
+RUN_AHEAD = 2
 
 
 class GraphedTrainStep:
@@ -284,10 +286,12 @@ class GraphedTrainStep:
     restored with the checkpoint's RNG bundle).  The gradient exchange and the optimizer stay outside the graph."""
 
     def __init__(self, model, criterion, samples, targets, patch_targets=None, patch_output_type=None, warmup=2,
-                 split_for_sync=False, optimizer=None):
+                 split_for_sync=False, optimizer=None, opt_overlap=1, opt_overlap_blocks=256):
         """split_for_sync: capture the backward as TWO graphs cut after the last stage (model.split_plan()), so that
         step_with_sync() can all-reduce the finished tail of the gradient arena (most of the parameters) while the rest
-        of the backward -- most of the time -- is still running."""
+        of the backward -- most of the time -- is still running.
+        opt_overlap / opt_overlap_blocks (with optimizer): number of arena ranges updated early, beside the rest of the backward,
+        and the workgroup cap of those updates (see below)."""
         self.model, self.criterion, self.pot = model, criterion, patch_output_type
         self.graph_b, self.split, self.more_graphs, self.ranges = None, None, [], []
         self._inflight = []
@@ -297,28 +301,11 @@ class GraphedTrainStep:
         self.optimizer = optimizer if (optimizer is not None and hasattr(optimizer, "step_device")) else None
         if self.optimizer is not None and split_for_sync:
             raise ValueError("optimizer-in-graph is for one rank; with a gradient exchange step the optimizer after step_with_sync")
-        # deferred form (VITRES_OPT_DEFER=1, nets with a spatial reduction): the graph OPENS with the update of the previous replay's
-        # gradients -- arena head on the main stream, the rest (stages 2.., heads: most parameters) on the side stream beside the
-        # first stage's forward -- instead of closing with a 0.36 ms pass nothing overlaps.  Same sequence of updates; the LAST one
-        # is applied by finish_update() (call it before evaluating, checkpointing or changing the learning rate: end of an
-        # epoch); this object then calls optimizer.prepare_step() itself.  Measured round 3: 7.73 - 7.84 against 7.80 - 7.85 ms
-        # (the 8192-workgroup update takes the CUs first -- the forward's first GEMM waits 350 us behind it -- and capped at
-        # 256 - 2048 workgroups, VITRES_ADAMW_BLOCKS, the forward slows by what the update reads): within noise, so opt-in.
-        self.defer, self._pending = None, False
-        if self.optimizer is not None and os.environ.get("VITRES_OPT_DEFER", "0") != "0" and hasattr(model, "split_plan"):
-            model._ensure_arena(samples.device)
-            cuts3 = model.split_plan(parts=99)
-            has_sr = any(type(b).__name__ == "SpatialReductionPatchEmbedding" for b in getattr(model, "blocks", []))
-            if has_sr and isinstance(cuts3, list) and cuts3 and cuts3[-1][1] % 8 == 0:
-                self.defer = cuts3[-1][1]                          # arena offset of the first spatial reduction
-                # checkpoint_dict / evaluate / FlatAdamW.state_dict refuse to run while an update is pending (weights one step behind)
-                self.optimizer._graph_pending = lambda: self._pending
-                model._graph_pending = self.optimizer._graph_pending
+        self.defer = None                    # (the deferred in-graph update is gone; bench.py still reads the attribute)
         # soft-target CE is the training loss of every shipped recipe (main.py:390-398): the whole step then runs without
         # autograd and without torch glue between the heads and the backward (model.loss_and_grad / vr_softce_train)
         from .losses import SoftTargetCrossEntropy
-        self.fused_loss = isinstance(criterion, SoftTargetCrossEntropy) and hasattr(model, "loss_and_grad") and \
-            os.environ.get("VITRES_FUSED_LOSS", "1") != "0"
+        self.fused_loss = isinstance(criterion, SoftTargetCrossEntropy) and hasattr(model, "loss_and_grad")
         self.x, self.t = samples.clone(), targets.clone()
         self.pt = patch_targets.clone() if patch_targets is not None else None
         B = samples.shape[0]
@@ -370,39 +357,33 @@ class GraphedTrainStep:
             if self.optimizer is not None:
                 self.optimizer.prepare_step()                      # allocates / fills the device hyper-parameters (not captured)
                 self.optimizer._step -= 1
-                # VITRES_OPT_OVERLAP = number of arena ranges updated EARLY (0 off, 1 (default): head + last stage, 2: + the stage
+                # opt_overlap = number of arena ranges updated EARLY (0 off, 1 (default): head + last stage, 2: + the stage
                 # before; measured round 4: 7.47 -> 7.36 - 7.39 ms with 1 or 2, profiles/r04_optimizer_overlap.txt):
                 # the backward is cut in front of the spatial reductions (model.split_plan) and the range a part completes is
                 # updated on the weight gradients' side stream -- IN ORDER with the groups there: a third branch would land on
-                # their hardware queue in front of them (round 4) -- by at most VITRES_OPT_OVERLAP_BLOCKS resident workgroups
+                # their hardware queue in front of them (round 4) -- by at most opt_overlap_blocks resident workgroups
                 # (256: one per CU; the uncapped update took the chip and cost more than it hid in rounds 1 - 3), beside the rest
                 # of the backward; what is left (the first stage + embedding) follows the backward at full width.
-                n_early = int(os.environ.get("VITRES_OPT_OVERLAP", "1"))
-                opt_cut = None
-                if n_early > 0 and self.defer is None:             # (the deferred form updates beside the NEXT forward: no cut)
-                    oc = model.split_plan(parts=max(n_early + 1, 3))
-                    oc = oc[:n_early] if isinstance(oc, list) else None
+                if opt_overlap > 0:
+                    oc = model.split_plan(parts=max(opt_overlap + 1, 3))
+                    oc = oc[:opt_overlap] if isinstance(oc, list) else None
                     if oc:
                         opt_cut = oc
                         model._bwd_split = [c for c, _ in oc]
                         model._bwd_join_parts = False              # the next part follows in the same capture
-            if self.defer is not None:
-                opt_cut = None
-                model._deferred_update = (self.optimizer, self.defer)
             with torch.cuda.graph(self.graph):
                 if self.keep_static is not None:
                     model.attach_plan_buffer(plan, self.keep_static, self._plan_nk)
                 plan.embed_col = self.col_static
                 self.loss = self._step_body(plan)
-                if self.optimizer is not None and self.defer is None:
+                if self.optimizer is not None:
                     from . import functional as Fn
                     n_arena = model._arena["flat"].numel()
                     if opt_cut is not None and getattr(model, "_bwd_state", None) is not None:
-                        cap = int(os.environ.get("VITRES_OPT_OVERLAP_BLOCKS", "256"))
                         hi = n_arena
                         for _, lo in opt_cut:                          # ranges complete from the arena's end backwards
                             if Fn.OVERLAP:
-                                Fn.on_side(lambda lo=lo, hi=hi: self.optimizer.step_device(lo, hi, max_blocks=cap), after_all_sides=True)
+                                Fn.on_side(lambda lo=lo, hi=hi: self.optimizer.step_device(lo, hi, max_blocks=opt_overlap_blocks))
                             else:
                                 self.optimizer.step_device(lo, hi)
                             hi = lo
@@ -419,7 +400,6 @@ class GraphedTrainStep:
         finally:
             model._bwd_split = None
             model._bwd_join_parts = True
-            model._deferred_update = None
         if self.more_graphs:
             self.graph_b = self.more_graphs[0]
             end = model._arena["gcur"].numel()
@@ -467,10 +447,6 @@ class GraphedTrainStep:
         plan = self.model.sample_plan(samples.shape[0])
         if rng is not None:
             torch.random.set_rng_state(rng)
-        probe = self._gap_probe
-        if probe is not None:                                      # dev aid (VITRES_DBG_GAP2): GPU time of the phases of one call
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-            ev[0].record()
         if self.keep_static is not None:
             flat, _ = self.model.plan_host_buffer(plan)
             slot = self._stage[self._stage_i % len(self._stage)]
@@ -478,15 +454,10 @@ class GraphedTrainStep:
             if slot[1] is not None:
                 slot[1].synchronize()                             # the host runs ahead of the device: the block's last copy is done?
             slot[0].numpy()[:] = flat
-            if PLAN_COPY_KERNEL:
-                from . import kernels as K
-                K.copy_i32_from_pinned(slot[0], self.keep_static.view(-1))
-            else:
-                self.keep_static.copy_(slot[0], non_blocking=True)
+            from . import kernels as K
+            K.copy_i32_from_pinned(slot[0], self.keep_static.view(-1))      # (a kernel reading pinned memory, not a memcpy)
             slot[1] = torch.cuda.Event()
             slot[1].record()
-        if probe is not None:
-            ev[1].record()
         if self.col_static is not None:
             self._gather(samples, plan)                           # reads the caller's tensor directly
         elif samples.data_ptr() != self.x.data_ptr():
@@ -495,53 +466,25 @@ class GraphedTrainStep:
             self.t.copy_(targets, non_blocking=True)
             if self.pt is not None:
                 self.pt.copy_(patch_targets, non_blocking=True)
-        if self.defer is not None:
-            self.optimizer.prepare_step(noop=not self._pending)   # the update this replay opens with: the previous replay's gradients
-            self._pending = True
-        # bounded run-ahead: the host needs ~3 ms for a 7.5 ms step, so left alone it queues replay after replay until the runtime's
-        # queue limit stops it (~25 steps in); on the way the runtime grows its per-launch resources a few times, and each growth
-        # stalls the device for ~1 ms (six 8.3 - 8.9 ms steps among the first 26 of a run, none after).  RUN_AHEAD replays in
-        # flight keep the device fed with the host two steps ahead from the third step on (VITRES_RUN_AHEAD, 0 = unbounded).
-        if RUN_AHEAD > 0:
-            if len(self._inflight) >= RUN_AHEAD:
-                self._inflight.pop(0).synchronize()
-        if probe is not None:
-            ev[2].record()
+        if len(self._inflight) >= RUN_AHEAD:                       # (bounded run-ahead: RUN_AHEAD)
+            self._inflight.pop(0).synchronize()
         self.graph.replay()
         self.model._stem_fold = None                               # (stem.drop_fold: the replay moved BatchNorm's running statistics)
         for k, g in enumerate(self.more_graphs):
             if self._sync is not None:                            # the arena range of the part just replayed is final: exchange it now
                 self._works.append(self._sync.all_reduce_range(*self.ranges[k]))
             g.replay()
-        if probe is not None:
-            ev[3].record()
-            probe.append(ev)
-        if RUN_AHEAD > 0:
-            e_done = torch.cuda.Event()
-            e_done.record()
-            self._inflight.append(e_done)
+        e_done = torch.cuda.Event()
+        e_done.record()
+        self._inflight.append(e_done)
         return self.loss
 
     def finish_update(self):
-        """Deferred optimizer-in-graph: apply the update of the last replay's gradients now (eagerly).  No-op otherwise."""
-        if self.defer is not None and self._pending:
-            self.optimizer.prepare_step()
-            self.optimizer.step_device(0, self.model._arena["flat"].numel())
-            self._pending = False
+        """No-op: every replay's optimizer update is complete with the replay itself (kept for callers that call it before
+        evaluating, checkpointing or changing the learning rate, as the removed deferred update required)."""
 
     _sync, _works = None, ()
     _inflight = None
-    _gap_probe = [] if os.environ.get("VITRES_DBG_GAP2") else None
-
-    def gap_report(self, skip=10):
-        """VITRES_DBG_GAP2: average GPU ms of [plan copy | gather + target copies | graph replay | end of a call -> start of the next]."""
-        pr = self._gap_probe[skip:] if self._gap_probe else []
-        if len(pr) < 2:
-            return None
-        n = len(pr)
-        seg = [sum(e[k].elapsed_time(e[k + 1]) for e in pr) / n for k in range(3)]
-        seg.append(sum(pr[i][3].elapsed_time(pr[i + 1][0]) for i in range(n - 1)) / (n - 1))
-        return [round(v, 4) for v in seg]
 
     def step_with_sync(self, grad_sync, samples, targets, patch_targets=None, average=True, **kw):
         """Replay + data-parallel gradient exchange: with split_for_sync the all-reduce of the last stage's gradients
@@ -640,9 +583,6 @@ def evaluate(data_loader, model, device, print_freq=100, logger=None):
     criterion = torch.nn.CrossEntropyLoss()
     print_out = logger.info if logger else print
     meters = defaultdict(Meter)
-    if getattr(model, "_graph_pending", None) is not None and model._graph_pending():
-        raise RuntimeError("a deferred in-graph optimizer update is pending (weights one step behind): call "
-                           "GraphedTrainStep.finish_update() before evaluating")
     model.eval()
     for images, target in data_loader:
         images = images.to(device, non_blocking=True)

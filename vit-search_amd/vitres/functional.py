@@ -23,33 +23,33 @@ from . import kernels as K
 # At ViT-Res shapes each alone leaves most of the chip idle in its prologue / epilogue / tail phases, so they are
 # issued on two streams (parallel branches once the step is captured into a hipGraph) with `sched=1` launches
 # (one workgroup per tile) so the hardware interleaves both kernels' workgroups on every CU.
-OVERLAP = _os.environ.get('VITRES_OVERLAP', '3') != '0'
-DEFER_JOIN = _os.environ.get('VITRES_OVERLAP', '3') == '2'
-JOIN_PER_BLOCK = _os.environ.get('VITRES_OVERLAP', '3') == '3'
-FUSE_CAST = _os.environ.get('VITRES_FUSE_CAST', '1') != '0'      # LayerNorm backward also emits the next branch's gradient
-# vr_gemm_ln (gemm_nt_ln.hip): bit 0 = LayerNorm forward behind the Linear that produces its input, bit 1 = LayerNorm backward
-# behind the data-gradient GEMM that produces its gradient; whole-row tiles, so only widths <= VITRES_FUSE_LN_MAXN.  Round 2
+# VITRES_OVERLAP=0 (profiling passes: kernel times alone, through bench.py) issues everything in line on one stream; it is the
+# one environment variable the package reads besides VITRES_LIB (_lib.py).
+OVERLAP = _os.environ.get('VITRES_OVERLAP', '1') != '0'
+# vr_gemm_ln (gemm_nt_ln.hip): the LayerNorm forward behind the Linear that produces its input, and the LayerNorm backward
+# behind the data-gradient GEMM that produces its gradient; whole-row tiles, so only widths <= FUSE_LN_MAXN.  Round 2
 # (kernel rewritten as GEMM K loop + the LayerNorm kernels' row loop glued through LDS) measured inside the sr_tiny step:
 # backward fusion at width 256: 51 us against 28 + 36..50 us for the two kernels (8.34 -> 8.20 ms); forward fusion: proj (K <= 256)
 # 28 against 19.5 + 13.6 us, fc2 (K = 768: twelve single-buffered 64 x 256 slices) 45..49 against 32 + 13.6 us (a wash per kernel;
-# the step still prefers it, 8.12 against 8.17 ms, one launch less per block; VITRES_FUSE_LN_FWD_MAXK bounds the K it applies to);
+# the step still prefers it, 8.12 against 8.17 ms, one launch less per block; FUSE_LN_FWD_MAXK bounds the K it applies to);
 # width 512 (32 x 512 tiles, 260 of them at M = 8320) loses in both directions.
-FUSE_LN = int(_os.environ.get('VITRES_FUSE_LN', '3'))
-FUSE_LN_MAXN = int(_os.environ.get('VITRES_FUSE_LN_MAXN', '256'))
-FUSE_LN_FWD_MAXK = int(_os.environ.get('VITRES_FUSE_LN_FWD_MAXK', '4096'))
+# FUSE_LN = False (test aid): the separate LayerNorm kernels, the reference path the fused form is tested against.
+FUSE_LN = True
+FUSE_LN_MAXN = 256
+FUSE_LN_FWD_MAXK = 4096
 # LayerNorm weight / bias gradients: the workgroups of a LayerNorm backward add their column sums into LN_COPIES rows of
 # partial sums (grads["<weight key>.part"], [2, LN_COPIES, C], kept zero between backwards) instead of all of them into
 # the same 2C addresses; flush_ln_grads() folds the rows of every LayerNorm of a backward part in one launch.  vr_ln_bwd at
-# (128 x 257, 256): 33 -> 23 us.  0 / 1 = accumulate straight into the parameter gradients.
-LN_COPIES = int(_os.environ.get('VITRES_LN_COPIES', '64'))
-_DBG_SKIP_WGRAD = _os.environ.get('VITRES_DBG_SKIP_WGRAD', '0') != '0'
-_DBG_WGRAD_SCHED = int(_os.environ.get('VITRES_DBG_WGRAD_SCHED', '0'), 0)      # dev aid: OR-ed into the weight gradients' sched (64: 4-wave group kernel)
+# (128 x 257, 256): 33 -> 23 us.
+LN_COPIES = 64
+# test / tool aid: bits OR-ed into the sched of every weight-gradient launch (64: tn_body's group kernel; 0x10000: the 8-wave one)
+WGRAD_SCHED = 0
 _ln_pending = []
 
 
 def _ln_dst(grads, wk, bk):
     """(dw, db, copies) for the LayerNorm backward kernels."""
-    part = grads.get(wk + ".part") if LN_COPIES > 1 else None
+    part = grads.get(wk + ".part")
     if part is None:
         return grads[wk], grads[bk], 1
     _ln_pending.append((part[0], part[1], grads[wk], grads[bk]))
@@ -88,77 +88,42 @@ def reset_ln_grads(model=None):
     return dirty
 
 
-STEM_SIDE = _os.environ.get('VITRES_STEM_SIDE', '1') != '0'      # conv-stem weight gradients on the side stream (+2 % since SIDE_DEFER)
-_side_streams = {}
-
-
+_side_streams = {}       # device -> the side stream of the weight gradients
 _pending = []            # tensors the side stream may still be reading (current generation)
 _lagged = []             # [(event recorded on the side stream, tensors)]: generations whose join was postponed
-JOIN_LAG = int(_os.environ.get('VITRES_JOIN_LAG', '2'))   # branches a join may trail behind (0: join at once)
+JOIN_LAG = 2             # branches a join may trail behind
 
 
-N_SIDE = max(1, int(_os.environ.get('VITRES_SIDE_STREAMS', '1')))   # side streams used round-robin
-_rr = [0]
-
-
-def _sides(dev):
+def _side(dev):
     side = _side_streams.get(dev)
     if side is None:
-        side = _side_streams[dev] = [torch.cuda.Stream(device=dev) for _ in range(N_SIDE)]
+        side = _side_streams[dev] = torch.cuda.Stream(device=dev)
     return side
 
 
-# VITRES_SIDE_DEFER=1: the side launch is ENQUEUED after the next kernel(s) of the main chain (its dependency -- an event recorded
-# now -- is unchanged).  In a captured graph the fork node then lists the main chain's successor first; whether the hipGraph
-# executor keeps the first successor on the parent's hardware queue decides if the main chain pays a cross-queue handoff
-# (12-17 us measured) at every fork.
-SIDE_DEFER = _os.environ.get('VITRES_SIDE_DEFER', '1') != '0'
+# The side launch is ENQUEUED after the next kernel(s) of the main chain (its dependency -- an event recorded now -- is
+# unchanged).  In a captured graph the fork node then lists the main chain's successor first; whether the hipGraph executor keeps
+# the first successor on the parent's hardware queue decides if the main chain pays a cross-queue handoff (12-17 us measured) at
+# every fork.
 _deferred = []           # [(event on the main stream, side stream, fn)]
-
-
-def _run_side(side, fn):
-    # (launches on a side stream overlap the main chain's: they get their own stream-K workspace -- kernels.ws_role)
-    sides = _side_streams.get(side.device, ())
-    role = 1 + (sides.index(side) if side in sides else 0)
-    with torch.cuda.stream(side), K.ws_role(role):
-        fn()
-
-
-def _wait_other_sides(side):
-    # (N_SIDE > 1 only) work that consumes what EVERY side stream produced -- the in-graph AdamW range update reads gradients whose
-    # weight-gradient groups went round-robin over the side streams -- is ordered behind all of them, not just its own stream
-    for other in _side_streams.get(side.device, ()):
-        if other is not side:
-            side.wait_stream(other)
 
 
 def flush_side():
     while _deferred:
-        ev, side, fn, after_all = _deferred.pop(0)
+        ev, side, fn = _deferred.pop(0)
         side.wait_event(ev)
-        if after_all:
-            _wait_other_sides(side)
-        _run_side(side, fn)
+        # (launches on the side stream overlap the main chain's: they get their own stream-K workspace -- kernels.ws_role)
+        with torch.cuda.stream(side), K.ws_role(1):
+            fn()
 
 
-def on_side(fn, *keepalive, defer=True, after_all_sides=False):
-    """Run fn() on a side stream after everything queued so far on the current stream; the tensors it reads are kept
-    alive (so the caching allocator cannot hand them out again) until join_side().  defer=False: launch at once (callers whose
-    fn() must have RUN on the host when on_side returns, or with no main kernel following before the join).
-    after_all_sides: fn() also waits for everything already issued on the OTHER side streams (VITRES_SIDE_STREAMS > 1)."""
+def on_side(fn, *keepalive):
+    """Run fn() on the side stream after everything queued so far on the current stream; the tensors it reads are kept
+    alive (so the caching allocator cannot hand them out again) until join_side()."""
     main = torch.cuda.current_stream()
-    sides = _sides(main.device)
-    side = sides[_rr[0] % len(sides)]
-    _rr[0] += 1
-    if SIDE_DEFER and defer:
-        flush_side()                       # the previous one: at least one main kernel has been enqueued since
-        _deferred.append((main.record_event(), side, fn, after_all_sides))
-    else:
-        flush_side()
-        side.wait_stream(main)
-        if after_all_sides:
-            _wait_other_sides(side)
-        _run_side(side, fn)
+    side = _side(main.device)
+    flush_side()                           # the previous one: at least one main kernel has been enqueued since
+    _deferred.append((main.record_event(), side, fn))
     _pending.extend(keepalive)
 
 
@@ -166,7 +131,7 @@ def on_side(fn, *keepalive, defer=True, after_all_sides=False):
 # gradient and the small reductions that close a backward run beside the first block's weight-gradient group instead of behind
 # one another on the main queue.  (Measured and dropped: AdamW over finished arena ranges on an "opt" stream OF ITS OWN beside the
 # rest of the backward -- 7.52 -> 7.98 ms however the update was throttled.  What ships is the same update issued IN ORDER on the
-# weight gradients' side stream: engine.GraphedTrainStep, VITRES_OPT_OVERLAP, 7.47 -> 7.37 ms.)
+# weight gradients' side stream: engine.GraphedTrainStep(opt_overlap=), 7.47 -> 7.37 ms.)
 _aux_streams = {}
 _aux_used = set()
 _AUX_ROLE = {}           # stream-K workspace role of each auxiliary stream (kernels.ws_role)
@@ -179,16 +144,13 @@ def aux_stream(dev, name):
     return st
 
 
-def on_aux(name, fn, *keepalive, after_side=False):
-    """Run fn() on the auxiliary stream `name` after everything queued so far on the current stream (and, after_side, on the
-    side streams: weight gradients already launched there).  Joined by join_side(); keepalive as on_side."""
+def on_aux(name, fn, *keepalive):
+    """Run fn() on the auxiliary stream `name` after everything queued so far on the current stream.  Joined by join_side();
+    keepalive as on_side."""
     flush_side()
     main = torch.cuda.current_stream()
     st = aux_stream(main.device, name)
     st.wait_stream(main)
-    if after_side:
-        for side in _side_streams.get(main.device, ()):
-            st.wait_stream(side)
     with torch.cuda.stream(st), K.ws_role(_AUX_ROLE.setdefault(name, 8 + len(_AUX_ROLE))):
         fn()
     _aux_used.add((main.device, name))
@@ -202,7 +164,8 @@ def join_side():
     flush_side()
     if _pending or _side_streams or _aux_used:         # (CPU runs never get here: nothing was ever put on a side stream)
         main = torch.cuda.current_stream()
-        for side in _side_streams.get(main.device, ()):
+        side = _side_streams.get(main.device)
+        if side is not None:
             main.wait_stream(side)
         for key in [k for k in _aux_used if k[0] == main.device]:
             main.wait_stream(_aux_streams[key])
@@ -216,20 +179,17 @@ def join_side_lagged():
     chain would sit idle behind: ~18 us of nothing running per join in the captured graph), record where the side stream is
     and wait for the point recorded JOIN_LAG branches ago -- long finished by now.  The tensors of the postponed generations
     stay alive meanwhile (one or two branches' worth, so buffers still recycle through the Infinity Cache)."""
-    if JOIN_LAG <= 0:
-        return join_side()
     flush_side()
     main = torch.cuda.current_stream()
-    sides = _side_streams.get(main.device)
-    if sides is None:
+    side = _side_streams.get(main.device)
+    if side is None:
         _pending.clear()
         return
-    _lagged.append(([sd.record_event() for sd in sides], list(_pending)))
+    _lagged.append((side.record_event(), list(_pending)))
     _pending.clear()
     while len(_lagged) > JOIN_LAG:
-        evs, _keep = _lagged.pop(0)
-        for ev in evs:
-            main.wait_event(ev)
+        ev, _keep = _lagged.pop(0)
+        main.wait_event(ev)
 
 
 def _overlap(x):
@@ -272,9 +232,9 @@ def linear_wgrad(dy, x, dw, M, N_out, K_in, lddy, ldx, ldw=None, a_map=None, b_m
         K.gemm(dy, x, dw, **kw)
 
 
-# VITRES_WGRAD_GROUP=1: the four weight gradients of a transformer block (fc2, fc1, proj, qkv) are issued as ONE vr_gemm_group
-# launch on the side stream once the last of their operands (dqkv) exists, instead of four launches of ~200 workgroups each.
-WGRAD_GROUP = _os.environ.get('VITRES_WGRAD_GROUP', '1') != '0'
+# The four weight gradients of a transformer block (fc2, fc1, proj, qkv) are issued as ONE vr_gemm_group launch on the side
+# stream once the last of their operands (dqkv) exists, instead of four launches of ~200 workgroups each (GPU runs; on the CPU
+# each Linear's weight gradient runs on its own).
 _block_wgrads = []       # collected (dy, x, dw, kwargs) of the block being walked backwards
 
 def flush_wgrads():
@@ -283,11 +243,6 @@ def flush_wgrads():
         return
     calls = list(_block_wgrads)
     del _block_wgrads[:]
-    if _DBG_SKIP_WGRAD:                                     # timing experiment only (wrong gradients): the main chain alone
-        if _os.environ.get('VITRES_DBG_SKIP_WGRAD') == '2':  # ... with the fork / join edges kept (a one-element kernel on the side)
-            t0 = calls[0][0]
-            on_side(lambda: t0.view(-1)[:1].add_(0), t0)
-        return
     if not OVERLAP:                                         # single-stream runs (profiling passes): same kernel, in line
         return K.gemm_group(calls)
     on_side(lambda: K.gemm_group(calls), *[t_ for c_ in calls for t_ in c_[:2]])
@@ -297,7 +252,7 @@ def flush_wgrads():
 # transformer block halves
 # --------------------------------------------------------------------------------------------------
 def _ln_fusable(a, C, next_ln):
-    return next_ln is not None and (FUSE_LN & 1) and C <= FUSE_LN_MAXN and a.shape[-1] <= FUSE_LN_FWD_MAXK and \
+    return next_ln is not None and FUSE_LN and C <= FUSE_LN_MAXN and a.shape[-1] <= FUSE_LN_FWD_MAXK and \
         K.gemm_ln_supported(a, C, C)
 
 
@@ -343,35 +298,21 @@ def attn_branch_bwd(g, saved, p, grads, cfg, embed_keep, attn_keep, out_keep, sc
     dt = cfg["dtype"]
     ov = _overlap(g)
     sch = 1 if ov else 0
-    wsch = sch | _DBG_WGRAD_SCHED
+    wsch = sch | WGRAD_SCHED
     if gt is None:
         gt = K.scale_mask_cast(g, scale, out_keep, N, dt)                   # d(branch output), compute dtype
 
-    grp = _block_wgrads if (WGRAD_GROUP and g.is_cuda) else None
-    mg = K.M_GROUPS[0]                 # (now: the closures below may run after the backward has returned)
-
-    def wgrad_proj():
-        linear_wgrad(gt, o, grads["proj.w"], M, C, HD, C, HD, db=grads["proj.b"], keep_rows=out_keep, keep_cols=attn_keep,
-                     tokens_per_sample=N, sched=wsch, collect=grp, m_groups=mg)
-    if grp is not None or not ov:
-        wgrad_proj()
-    else:
-        on_side(wgrad_proj, gt)
+    grp = _block_wgrads if g.is_cuda else None
+    linear_wgrad(gt, o, grads["proj.w"], M, C, HD, C, HD, db=grads["proj.b"], keep_rows=out_keep, keep_cols=attn_keep,
+                 tokens_per_sample=N, sched=wsch, collect=grp)
     d_o = torch.empty((B, N, HD), dtype=dt, device=x.device)
     linear_dgrad(gt, p["proj"], d_o, M, HD, C, C, HD, keep_n=attn_keep, rows_in=N, keep_k=out_keep, sched=sch)
     dqkv = K.attn_bwd(qkv, o, d_o, lse, attn_keep, B, N, H, D, cfg["scale"])
-
-    def wgrad_qkv():
-        linear_wgrad(dqkv, y, grads["qkv.w"], M, 3 * HD, C, 3 * HD, C, db=grads["qkv.b"], keep_rows=attn_keep,
-                     keep_cols=embed_keep, row_period=HD, tokens_per_sample=N, sched=wsch, collect=grp, m_groups=mg)
+    linear_wgrad(dqkv, y, grads["qkv.w"], M, 3 * HD, C, 3 * HD, C, db=grads["qkv.b"], keep_rows=attn_keep,
+                 keep_cols=embed_keep, row_period=HD, tokens_per_sample=N, sched=wsch, collect=grp)
     if grp is not None:
-        wgrad_qkv()
         flush_wgrads()                                      # fc2, fc1 (MLP branch), proj, qkv: every operand exists now
-    elif ov:
-        on_side(wgrad_qkv, dqkv)
-    else:
-        wgrad_qkv()
-    if (FUSE_LN & 2) and C <= FUSE_LN_MAXN and p["qkv"].w_t is not None and K.gemm_ln_supported(dqkv, C, C):
+    if FUSE_LN and C <= FUSE_LN_MAXN and p["qkv"].w_t is not None and K.gemm_ln_supported(dqkv, C, C):
         dw, db, cp = _ln_dst(grads, "n1w", "n1b")
         out = K.gemm_ln_bwd(dqkv, p["qkv"].w_t, x, p["n1w"], mean, rstd, embed_keep, g, dw, db,
                             next_cast=next_cast, M=M, N=C, K=3 * HD, lda=3 * HD, ldb=p["qkv"].ld_t, rows_in=N,
@@ -382,7 +323,7 @@ def attn_branch_bwd(g, saved, p, grads, cfg, embed_keep, attn_keep, out_keep, sc
                      sched=sch)
         dw, db, cp = _ln_dst(grads, "n1w", "n1b")
         out = K.ln_bwd(dy, x, p["n1w"], mean, rstd, embed_keep, N, g, dw, db, next_cast=next_cast, copies=cp)
-    if ov and not DEFER_JOIN:
+    if ov:
         join_side_lagged()
     return out
 
@@ -427,34 +368,20 @@ def mlp_branch_bwd(g, saved, p, grads, cfg, embed_keep, mlp_keep, out_keep, scal
     M = B * N
     F = cfg["hidden"]
     dt = cfg["dtype"]
-    ov = _overlap(g)
-    sch = 1 if ov else 0
-    wsch = sch | _DBG_WGRAD_SCHED
+    sch = 1 if _overlap(g) else 0
+    wsch = sch | WGRAD_SCHED | K.reads_skipped()
     if gt is None:
         gt = K.scale_mask_cast(g, scale, out_keep, N, dt)
 
-    grp = _block_wgrads if (WGRAD_GROUP and g.is_cuda) else None
-    rsk, mg = K.reads_skipped(), K.M_GROUPS[0]            # (now: the closures below may run after the backward has returned)
-
-    def wgrad_fc2():
-        linear_wgrad(gt, h, grads["fc2.w"], M, C, F, C, F, db=grads["fc2.b"], keep_rows=out_keep, keep_cols=mlp_keep,
-                     tokens_per_sample=N, sched=wsch | rsk, collect=grp, m_groups=mg)
-    if ov and grp is None:
-        on_side(wgrad_fc2, gt)
-    else:
-        wgrad_fc2()
+    grp = _block_wgrads if g.is_cuda else None
+    linear_wgrad(gt, h, grads["fc2.w"], M, C, F, C, F, db=grads["fc2.b"], keep_rows=out_keep, keep_cols=mlp_keep,
+                 tokens_per_sample=N, sched=wsch, collect=grp)
     du = torch.empty((B, N, F), dtype=dt, device=x.device)
     linear_dgrad(gt, p["fc2"], du, M, F, C, C, F, dact_u=u, ldu=F, keep_n=mlp_keep, rows_in=N, keep_k=out_keep, sched=sch,
                  act=(2 if dt == torch.bfloat16 else 0))
-
-    def wgrad_fc1():
-        linear_wgrad(du, y, grads["fc1.w"], M, F, C, F, C, db=grads["fc1.b"], keep_rows=mlp_keep, keep_cols=embed_keep,
-                     tokens_per_sample=N, sched=wsch | rsk, collect=grp, m_groups=mg)
-    if ov and grp is None:
-        on_side(wgrad_fc1, du)
-    else:
-        wgrad_fc1()
-    if (FUSE_LN & 2) and C <= FUSE_LN_MAXN and p["fc1"].w_t is not None and K.gemm_ln_supported(du, C, C):
+    linear_wgrad(du, y, grads["fc1.w"], M, F, C, F, C, db=grads["fc1.b"], keep_rows=mlp_keep, keep_cols=embed_keep,
+                 tokens_per_sample=N, sched=wsch, collect=grp)
+    if FUSE_LN and C <= FUSE_LN_MAXN and p["fc1"].w_t is not None and K.gemm_ln_supported(du, C, C):
         dw, db, cp = _ln_dst(grads, "n2w", "n2b")
         out = K.gemm_ln_bwd(du, p["fc1"].w_t, x, p["n2w"], mean, rstd, embed_keep, g, dw, db,
                             next_cast=next_cast, M=M, N=C, K=F, lda=F, ldb=p["fc1"].ld_t, rows_in=N, keep_k=mlp_keep, copies=cp,
@@ -464,9 +391,7 @@ def mlp_branch_bwd(g, saved, p, grads, cfg, embed_keep, mlp_keep, out_keep, scal
         linear_dgrad(du, p["fc1"], dy, M, C, F, F, C, rows_in=N, keep_k=mlp_keep, keep_n=embed_keep, sched=sch | K.reads_skipped())
         dw, db, cp = _ln_dst(grads, "n2w", "n2b")
         out = K.ln_bwd(dy, x, p["n2w"], mean, rstd, embed_keep, N, g, dw, db, next_cast=next_cast, copies=cp)
-    if ov and not DEFER_JOIN and not JOIN_PER_BLOCK:
-        join_side_lagged()
-    return out
+    return out                             # (the block's join follows its attention branch)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -556,12 +481,11 @@ def embed0_fwd(img, p, cfg, keep, save, sample_map=None, col=None):
 # Token split of the patch-embedding weight gradient (2 x 5 tiles of 128^2 over 32 768 tokens): the kernel's coarse rule gives it
 # 160 workgroups walking 32 slices each (103 us, and it was the first kernel of a serial step tail); EMBED_WGRAD_SLICES slices
 # per workgroup -> 4x the workgroups, each paying |tile| x 4 B of atomics (42 MB in all at 8).
-EMBED_WGRAD_SLICES = int(_os.environ.get('VITRES_EMBED_WGRAD_SLICES', '8'))
+EMBED_WGRAD_SLICES = 8
 # The end of a backward -- patch-embedding weight gradient, positional-embedding sums, LayerNorm partial-row folds -- runs on the
 # auxiliary stream "tail" beside the first block's weight-gradient group (they feed nothing but the optimizer); in line on the main
 # stream it was 0.15 ms of kernels one after another with nothing beside them (round 3).  On THREE branches (the sums on the main
 # stream) the third lands on the weight gradients' hardware queue in front of the last two groups: +0.1 ms (round 4).
-TAIL_AUX = True
 
 
 def embed0_bwd(g, saved, p, grads, cfg, keep, gt=None, wgrad=True, pos=True):
@@ -577,7 +501,7 @@ def embed0_bwd(g, saved, p, grads, cfg, keep, gt=None, wgrad=True, pos=True):
     if gt is None:
         gt = K.scale_mask_cast(g, None, keep, N, dt)
     split = 0
-    if EMBED_WGRAD_SLICES > 0 and g.is_cuda and dt == torch.bfloat16:
+    if g.is_cuda and dt == torch.bfloat16:
         split = max(1, -(-(B * P) // (64 * EMBED_WGRAD_SLICES)))
     if wgrad:
         linear_wgrad(gt, col, grads["proj.w"], B * P, C, ldk, C, ldk, a_map=(P, N, T), db=grads["proj.b"], split=split)

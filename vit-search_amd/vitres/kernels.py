@@ -49,14 +49,13 @@ def _rm(m):
 
 
 # Workspaces of the split-K GEMM form (vr_gemm_args.ws): one per (device, role).  A role is a chain of launches that never overlap
-# one another: 0 = the main stream, 1.. = the side streams of vitres.functional (which switches the role around what it runs
-# there).  Created zeroed on first use -- outside graph capture (engine.GraphedTrainStep calls ensure_workspaces first): a launch
+# one another: 0 = the main stream, 1 = the side stream of vitres.functional, 8.. = its auxiliary streams (it switches the role
+# around what it runs there).  Created zeroed on first use -- outside graph capture (engine.GraphedTrainStep calls ensure_workspaces first): a launch
 # that finds none while capturing simply runs without tile sharing.
 _WS = {}
 _WS_ROLE = [0]
-# dev aid (A/B inside the step): bits OR-ed into vr_gemm_args.sched / value of k_shares of every forward / data-gradient launch
-_DBG_SCHED_OR = int(__import__("os").environ.get("VITRES_DBG_SCHED_OR", "0"), 0)
-_DBG_K_SHARES = int(__import__("os").environ.get("VITRES_DBG_K_SHARES", "0"))
+# test / tool aid: k_shares of every forward / data-gradient launch that does not pass its own (0: the library's rule)
+K_SHARES = 0
 
 
 class ws_role:
@@ -88,7 +87,6 @@ def ensure_workspaces(dev, roles=(0, 1)):
 # Architecture groups of the batch being processed (vr_gemm_args.m_groups): the model sets it from its plan at the start of a
 # forward / backward (G = B / example_per_arch contiguous groups of samples in the arch-grouped execution order, each with its own
 # keep rows); every GEMM that carries keep arrays passes it on, so that the kernels deal every group to every XCD.
-# VITRES_GROUP_INTERLEAVE=0 keeps the plain tile order (measurement).
 M_GROUPS = [1]
 # The model vouches (vit_sr_supernet.sample_plan -> plan.skip_writes) that every tile / token split of the bf16 kernels sees ONE
 # architecture of the batch being processed and that every masked Linear of the network is one the group-pure kernels cover: the
@@ -105,10 +103,9 @@ def reads_skipped():
     return READS_SKIPPED_BIT if WRITE_SKIP[0] else 0
 
 
-# test aid (tests/test_gpu_model.py): fill the output of every launch that may leave tiles unwritten with NaN first -- a reader of
+# test aid (tests/test_gpu_fullsize.py): fill the output of every launch that may leave tiles unwritten with NaN first -- a reader of
 # an unwritten tile then changes the loss / gradients instead of quietly reading whatever the arena held
-DBG_POISON = [__import__("os").environ.get("VITRES_DBG_POISON", "0") != "0"]
-_GROUP_INTERLEAVE = __import__("os").environ.get("VITRES_GROUP_INTERLEAVE", "1") != "0"
+DBG_POISON = False
 
 
 def _gemm_args(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=False, out2=None, bias=None, pos=None,
@@ -120,15 +117,13 @@ def _gemm_args(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=Fals
         ws = _workspace(a.device) if (not a_trans and a.dtype == torch.bfloat16 and a.is_cuda and K >= 512 and k_shares != 1) else None
     if ws is not None:
         args.ws, args.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    args.ring, args.k_shares = ring, (k_shares or (_DBG_K_SHARES if not a_trans else 0))
-    if not a_trans:
-        sched |= _DBG_SCHED_OR
+    args.ring, args.k_shares = ring, (k_shares or (K_SHARES if not a_trans else 0))
     args.A, args.B, args.C, args.C2 = _p(a), _p(b), _p(out), _p(out2)
     args.bias, args.pos, args.scale, args.keep_n = _p(bias), _p(pos), _p(scale), _p(keep_n)
     args.resid, args.dact_u, args.bias_grad, args.keep_k = _p(resid), _p(dact_u), _p(bias_grad), _p(keep_k)
     args.n_period, args.k_period, args.sched = n_period, k_period, sched
     mg = M_GROUPS[0] if m_groups is None else m_groups      # (closures launched later pass the value of their own forward / backward)
-    args.m_groups = mg if (_GROUP_INTERLEAVE and (keep_k is not None or keep_n is not None) and rows_in > 0) else 0
+    args.m_groups = mg if ((keep_k is not None or keep_n is not None) and rows_in > 0) else 0
     if WRITE_SKIP[0] and (keep_k is not None or keep_n is not None) and rows_in > 0 and (mg <= 1 or args.m_groups > 1):
         args.sched |= SKIP_WRITES_BIT
     args.M, args.N, args.K = M, N, K
@@ -201,8 +196,9 @@ def gemm_ln_fwd(a, b, out, ln_w, ln_b, ln_keep, eps, *, M, N, K, lda, ldb, ldc, 
 # vr_gemm_ln_fold (rows of several 128-column tiles; narrower rows go to vr_gemm_ln) is OPT-IN: measured round 6 inside the sr_tiny step
 # 7.51 against 6.97 ms (52 - 73 us per folded launch against 22 - 35 + 5 - 8 for the two kernels, profiles/r06_ln_fold.txt): the tiles'
 # fp32 rows must be visible to a workgroup on ANOTHER XCD inside the launch, i.e. stored write-through (partial-line writes to
-# memory) and waited for, and the last arriver's row loop is a tail nothing runs beside.
-LN_FOLD = __import__("os").environ.get("VITRES_LN_FOLD", "0") != "0"
+# memory) and waited for, and the last arriver's row loop is a tail nothing runs beside.  Set True by tests (the model-level
+# parity of the form).
+LN_FOLD = False
 
 
 def gemm_ln_fold_fwd(a, b, out, ln_w, ln_b, ln_keep, eps, *, M, N, K, lda, ldb, ldc, bias=None, scale=None, keep_n=None,
@@ -269,7 +265,7 @@ def gemm(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=False, out
                       atomic=atomic, split_k=split_k, rows_in=rows_in, a_map=a_map, b_map=b_map, c_map=c_map,
                       bias_grad=bias_grad, keep_k=keep_k, n_period=n_period, k_period=k_period, sched=sched, ws=ws,
                       ring=ring, k_shares=k_shares, m_groups=m_groups)
-    if DBG_POISON[0] and (args.sched & SKIP_WRITES_BIT) and keep_n is not None and not a_trans and resid is None and \
+    if DBG_POISON and (args.sched & SKIP_WRITES_BIT) and keep_n is not None and not a_trans and resid is None and \
             out.dtype == torch.bfloat16:
         out.fill_(float("nan"))
         if out2 is not None:

@@ -55,9 +55,10 @@ def trunc_normal_(t, std):
     return nn.init.trunc_normal_(t, mean=0., std=std, a=-2., b=2.)
 
 
-_SKIP_DROPPED = __import__("os").environ.get("VITRES_SKIP_DROPPED_LAYERS", "1") != "0"
-# VITRES_SKIP_MASKED_WRITES=0: the masked GEMMs store the zeros of their fully masked tiles (measurement / A-B aid)
-_SKIP_WRITES = __import__("os").environ.get("VITRES_SKIP_MASKED_WRITES", "1") != "0"
+# test aids: False is the computing path the skipping one is tested against -- _SKIP_DROPPED: dropped layers / samples are computed
+# and multiplied by zero; _SKIP_WRITES: the masked GEMMs store the zeros of their fully masked tiles
+_SKIP_DROPPED = True
+_SKIP_WRITES = True
 
 class BypassBlock(nn.Module):
     """Removed transformer block (exists == 0): identity, resets the layer mask (reference :50-56)."""
@@ -345,17 +346,13 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         # transposed bf16 shadows W^T [in, roundup(out, 8)] (one batched transposing cast per step).  Round 2: the data-gradient
         # GEMMs read the forward's weight itself (vr_gemm b_trans on the LDS-DMA kernel: k-major weight slices, transposing LDS
         # reads); only the Linears whose data gradient runs inside vr_gemm_ln (qkv / fc1 of the narrow first stage) still get a
-        # transposed copy.  VITRES_WT_SHADOWS=all: every Linear (round-1 layout), none: no copies (no fused LayerNorm backward)
-        import os as _os
-        which = a["wt_mode"] = _os.environ.get("VITRES_WT_SHADOWS", "fused")
-        if self.compute_dtype == torch.bfloat16 and which != "none":
+        # transposed copy.
+        if self.compute_dtype == torch.bfloat16:
             entries, tot_t = [], 0
             for name, mod in self.named_modules():
                 fused = (name.endswith("attn.qkv") or name.endswith("mlp.fc1")) and isinstance(mod, nn.Linear) and \
                     mod.in_features <= Fn.FUSE_LN_MAXN
-                if which != "all" and not fused:
-                    continue
-                if isinstance(mod, nn.Linear) and id(mod.weight) in a["index"]:
+                if fused and id(mod.weight) in a["index"]:
                     w = mod.weight
                     out_f, in_f = w.shape
                     ld_t = (out_f + 7) // 8 * 8
@@ -410,7 +407,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         (functional.LN_COPIES; one allocation for the whole network, made before any capture can be running)."""
         a = self._arena
         parts = a.get("ln_parts")
-        if parts is None or a.get("ln_copies") != Fn.LN_COPIES:
+        if parts is None:
             norms = [m for m in self.modules() if isinstance(m, (nn.LayerNorm, MaskedLayerNorm)) and m.weight is not None]
             total = sum(2 * Fn.LN_COPIES * m.weight.numel() for m in norms)
             flat = torch.zeros(total, dtype=torch.float32, device=a["flat"].device)
@@ -419,7 +416,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                 n = 2 * Fn.LN_COPIES * m.weight.numel()
                 parts[id(m.weight)] = flat[off:off + n].view(2, Fn.LN_COPIES, m.weight.numel())
                 off += n
-            a["ln_parts"], a["ln_parts_flat"], a["ln_copies"] = parts, flat, Fn.LN_COPIES
+            a["ln_parts"], a["ln_parts_flat"] = parts, flat
         return parts
 
     # ---- host-side mask plan -----------------------------------------------------------------------
@@ -485,7 +482,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                 # multiplied by the layer mask) contributes exactly nothing -- no output, no parameter gradient: its attention / MLP
                 # widths are zeroed in the rows the KERNELS read (the sampled values, `groups`, are untouched), so that the masked-work
                 # rules skip the qkv / fc1 GEMMs, the attention cores and their backward for those samples instead of computing
-                # values the layer mask then discards (VITRES_SKIP_DROPPED_LAYERS=0: compute them)
+                # values the layer mask then discards (_SKIP_DROPPED = False: compute them)
                 if _SKIP_DROPPED and cur is not None and ka is not None and km is not None and np.any(np.asarray(cur) == 0):
                     ka = np.where(np.asarray(cur) > 0, ka, 0)
                     km = np.where(np.asarray(cur) > 0, km, 0)
@@ -751,12 +748,9 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             wsrc = self._wc(w)
             wperm = torch.empty((w.shape[0], 9 * w.shape[1]), dtype=wsrc.dtype, device=wsrc.device)
             K.relayout(wsrc, wperm, w.shape[0], w.shape[1], 9)              # (vr_relayout: no torch permute / copy kernels)
-            # (transposed copy for the data gradient only in the round-1 layout: the LDS-DMA kernel reads wperm itself, b_trans)
-            wperm_t = wperm.t().contiguous() if self.compute_dtype == torch.bfloat16 and wperm.shape[0] % 8 == 0 and \
-                self._arena.get("wt_mode") == "all" else None
+            # (no transposed copy: the data gradient's LDS-DMA kernel reads wperm itself, b_trans)
             return {"nw": blk.norm.weight.detach(), "nb": blk.norm.bias.detach(),
-                    "reduce": Fn.Weights(w, blk.patch_reduce.bias.detach(), wperm, wperm.shape[1], wperm_t,
-                                         wperm.shape[0]),
+                    "reduce": Fn.Weights(w, blk.patch_reduce.bias.detach(), wperm, wperm.shape[1]),
                     "token": self._lin(blk.token_transform), "pos": blk.pos_embed.detach()[0]}
         return None
 
@@ -798,21 +792,6 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         a = self._arena
         if save and Fn.reset_ln_grads(self) and a.get("ln_parts_flat") is not None:      # (a backward died: see _run_backward)
             a["ln_parts_flat"].zero_()
-        # engine.GraphedTrainStep(optimizer=..., deferred): the PREVIOUS replay's AdamW update opens this forward -- the head of the
-        # arena (tokens, positional embedding, patch embedding, first stage) here, the rest (most parameters) on the side stream
-        # beside the first stage, which does not read them; joined with side_prep in front of the first spatial reduction
-        du = getattr(self, "_deferred_update", None)
-        du_side = None
-        if du is not None:
-            opt_, lo_ = du
-            n_ = a["flat"].numel()
-            if (save and self.compute_dtype == torch.bfloat16 and a["tr"] is not None and Fn.OVERLAP and a["flat"].is_cuda and
-                    0 < lo_ < n_):
-                Fn.join_side()             # (a previous forward's side work)
-                opt_.step_device(0, lo_)
-                du_side = (opt_, lo_, n_)
-            else:
-                opt_.step_device(0, n_)
         if self.compute_dtype == torch.bfloat16:
             if Fn.OVERLAP and a["flat"].is_cuda:
                 Fn.join_side()             # a previous forward's side work (if its backward never ran)
@@ -849,8 +828,6 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                 fresh = a["gflat"] is not None and all(p_.grad is None for p_ in a["params"])
 
                 def side_prep():
-                    if du_side is not None:
-                        du_side[0].step_device(du_side[1], du_side[2])
                     K.cast_transpose_batch(a["flat"], a["shadow_t"], a["tr"])
                     for blk_ in self.blocks:
                         if isinstance(blk_, SpatialReductionPatchEmbedding):
@@ -913,7 +890,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                 h, sa, pre = Fn.attn_branch_fwd(h, p, cfg, ek, ka, ko, s1, save, pre=pre,
                                                 next_ln=(p["n2w"], p["n2b"], ek, cfg["eps"]))
                 if i == 0:
-                    Fn.flush_side()        # side_prep: enqueued after the main chain's first kernels (functional.SIDE_DEFER)
+                    Fn.flush_side()        # side_prep: enqueued after the main chain's first kernels (functional.on_side)
                 h, sm, pre = Fn.mlp_branch_fwd(h, p, cfg, ek, km, ko, s2, save, pre=pre, next_ln=first_ln(i + 1))
                 if save:
                     tape.append(("block", blk, p, cfg, (ek, ka, km, ko, s1, s2), sa, sm))
@@ -955,10 +932,9 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         stale = Fn.reset_ln_grads(self)
         Fn.claim_pending(self)
         Fn.join_side()                     # transposed weight shadows (issued beside the forward)
-        if Fn.LN_COPIES > 1:
-            self._ln_parts()
-            if stale:
-                a["ln_parts_flat"].zero_()
+        self._ln_parts()
+        if stale:
+            a["ln_parts_flat"].zero_()
         st = {"rtape": list(reversed(tape)), "plan": plan, "dcls": dcls, "dpat": dpat, "i": 0, "g": None, "gt": None,
               "ready": ready}
         # _bwd_split = j: stop after the head and blocks[j:]; the rest runs in resume_backward() (a second hipGraph, so that the
@@ -1031,7 +1007,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         def consumer_cast(i):
             """(DropPath scale, prefix keep) with which the entry after rtape[i] turns the gradient it receives into its
             compute-dtype branch gradient: LayerNorm backward emits that tensor in the same pass (vr_ln_bwd gt_out)."""
-            if i + 1 >= len(rtape) or not Fn.FUSE_CAST:
+            if i + 1 >= len(rtape):
                 return None
             e = rtape[i + 1]
             if e[0] == "block":
@@ -1043,7 +1019,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             return None
         gt = st["gt"]
         tail_aux = False
-        parts = a.get("ln_parts") if Fn.LN_COPIES > 1 else None
+        parts = a.get("ln_parts")
 
         def with_parts(grads, *pairs):
             if parts is not None:
@@ -1111,7 +1087,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                             K.relayout(wt, gv(w), w.shape[0], 1, k, src_ld=ld)   # drop the pad columns
                         if pos:
                             gv(self.tokens).copy_(gv(self.pos_embed)[:, 0:self.num_tokens, :])
-                    if Fn.TAIL_AUX and Fn.OVERLAP and g.is_cuda:
+                    if Fn._overlap(g):
                         # nothing downstream but the optimizer: the projection's weight gradient on the auxiliary stream beside the
                         # first block's last weight gradient, the small reductions meanwhile on the main stream
                         Fn.flush_wgrads()

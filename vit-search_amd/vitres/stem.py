@@ -72,18 +72,16 @@ def _bn_affine(z, bn, training):
 # Evaluation (frozen weights, running statistics): BatchNorm folds into the convolution in front of it -- the weights are scaled
 # per output channel by gamma / sqrt(var + eps), the shift becomes a bias, ReLU (and conv3's residual) move into the kernel's
 # epilogue: three bn_relu passes and the fp32 pre-BatchNorm tensors disappear (15 % of the candidate-scoring step was the stem).
-FOLD_BN = __import__("os").environ.get("VITRES_STEM_FOLD_BN", "1") != "0"
-# conv1 straight from the NCHW image (vr_conv1_direct) instead of im2col + GEMM; in training the im2col matrix is only built
-# in the backward, beside the data-gradient chain, for conv1's weight gradient
-DIRECT_CONV1 = __import__("os").environ.get("VITRES_STEM_DIRECT_CONV1", "1") != "0"
+# FOLD_BN = False (test aid): the unfolded path, the reference the folded one is tested against.
+FOLD_BN = True
+# conv1 runs straight from the NCHW image (vr_conv1_direct) wherever that kernel covers it, instead of im2col + GEMM; in training
+# the im2col matrix is only built in the backward, beside the data-gradient chain, for conv1's weight gradient
 # Opt-in (bf16 mode): store the pre-BatchNorm convolution outputs z in bf16 instead of fp32 -- they are read by four passes each
 # (statistics, normalise + ReLU, two in the backward; all sums stay fp32).  Measured: ref_tiny step 6.75 -> 6.58 ms, sr_tiny_mh
 # 9.89 -> 9.76 ms; but the worst parameter-gradient error of the 56-px conv-stem test nets against the fp32 reference grows
 # from 0.07 to 0.09 (bf16 has 3 mantissa bits fewer than the fp16 autocast gives the reference's convolutions), so the default
-# keeps fp32.
-Z_BF16 = __import__("os").environ.get("VITRES_STEM_Z_BF16", "0") != "0"
-# VITRES_STEM_PATCH_DIRECT=0: keep the unfold / fold passes around the 7 x 7 / stride-7 projection in training (measurement)
-PATCH_DIRECT = __import__("os").environ.get("VITRES_STEM_PATCH_DIRECT", "1") != "0"
+# keeps fp32 (a test / tool aid).
+Z_BF16 = False
 
 
 def drop_fold(model):
@@ -130,7 +128,7 @@ def _embed_conv_eval(model, x, p, cfg, keep):
     T = cfg.get("tokens", 1)
     N = P + T
     (w1, t1), (w2, t2), (w3, t3) = _folded_params(model)
-    if DIRECT_CONV1 and K.conv1_direct_supported(x, w1, m):
+    if K.conv1_direct_supported(x, w1, m):
         a1 = K.conv1_direct(x, w1, t1, True, dt)
     else:
         col1 = K.im2col3x3_image(x, 2, 32, dt)
@@ -172,7 +170,7 @@ def embed_conv_fwd(model, x, p, cfg, keep, save):
         z = torch.empty((R, m), dtype=zdt, device=x.device)
         K.gemm(col, w, z, M=R, N=m, K=ld, lda=ld, ldb=ld, ldc=m)
         return z
-    if DIRECT_CONV1 and K.conv1_direct_supported(x, p["w1"], m):
+    if K.conv1_direct_supported(x, p["w1"], m):
         col1 = None                                            # (built in the backward from the saved image)
         z1 = K.conv1_direct(x, p["w1"], None, False, zdt)
     else:
@@ -197,10 +195,10 @@ def embed_conv_fwd(model, x, p, cfg, keep, save):
         z3 = conv(col3, p["w3"], 9 * m)
     bn3 = _bn_affine(z3, pe.conv3.bn, tr)
     ps = model.patch_size // 2
-    # PATCH_DIRECT (round 4): the last BatchNorm + ReLU (+ skip) writes the projection's patchify operand itself and the backward
+    # Patch-direct (round 4): the last BatchNorm + ReLU (+ skip) writes the projection's patchify operand itself and the backward
     # reads the projection's data gradient where its GEMM leaves it (vr_bn_relu_patch / vr_bn_bwd_patch / vr_conv3x3_res_patch):
     # no patch_unfold / patch_fold pass (410 MB each way at B = 128).  Fast path only (direct convolutions, bf16).
-    pdirect = PATCH_DIRECT and direct and dt == torch.bfloat16 and Hm == g * ps and Wm == g * ps
+    pdirect = direct and dt == torch.bfloat16 and Hm == g * ps and Wm == g * ps
     if pdirect:
         colp = K.bn_relu_patch(z3, bn3[0], bn3[1], a1, B, Hm, Wm, ps, dt)
     else:
@@ -228,7 +226,7 @@ def embed_conv_bwd(model, gx, saved, p, cfg, keep, gv, gt=None):
     if gt is None:
         gt = K.scale_mask_cast(gx, None, keep, N, dt)
     # conv_proj
-    ov = Fn._overlap(gx) and Fn.STEM_SIDE
+    ov = Fn._overlap(gx)
     wtmp = K.zero_(torch.empty((C, ldk), dtype=torch.float32, device=dev))
 
     def wgrad_proj():
