@@ -16,7 +16,10 @@
  *   - All work is enqueued asynchronously on `stream`; no hidden synchronisation.
  *   - Return value: 0 = ok; > 0 = hipError_t of the launch; < 0 = argument validation
  *     (VR_EINVAL -1, VR_EALIGN -2, VR_EUNSUPPORTED -3).  No exceptions cross the ABI.
- *   - dtype codes: VR_F32 = 0 (exact-fp32 parity mode), VR_BF16 = 1 (raw bf16 bits, fast mode).
+ *   - dtype codes: VR_F32 = 0 (exact-fp32 parity mode), VR_BF16 = 1 (raw bf16 bits, fast mode), VR_F16 = 2 (raw IEEE
+ *     binary16 bits: the forward / evaluation forms only -- every backward / training entry returns VR_EUNSUPPORTED for it,
+ *     and so do the opt-in bf16 forms: K-split shares, the panel-resident GEMM, vr_gemm_ln_fold).  bf16 and fp16 never mix
+ *     in one call; the 3x3 convolution entries (which name only their output type) take fp16 operands when out_dtype is VR_F16.
  *   - `keep` arrays: int32[B], active channel-prefix length of each sample for that tensor
  *     (the reference's ChannelDrop prefix masks, nets/channel_drop.py:153-154); NULL = dense.
  *   - "rows_per_sample": number of consecutive rows (tokens) that belong to one sample.
@@ -35,6 +38,7 @@ typedef struct ihipStream_t* vr_stream_t; /* == hipStream_t */
 
 #define VR_F32 0
 #define VR_BF16 1
+#define VR_F16 2
 
 /* library / ABI version (major*1000 + minor) */
 int vr_version(void);
@@ -213,6 +217,9 @@ int vr_gemm_ln_fold(const vr_gemm_args* args, const vr_ln_epilogue* ln, vr_strea
 
 /* fp32 -> bf16 (round to nearest even), n elements.  Replaces autocast's per-op weight casts (engine.py:112). */
 int vr_cast_f32_bf16(const float* src, void* dst, int64_t n, vr_stream_t stream);
+/* fp32 -> fp16 (round to nearest even, overflow to +-inf, NaN kept: torch's .half()), n elements -- the weight shadow of the fp16
+ * evaluation mode. */
+int vr_cast_f32_f16(const float* src, void* dst, int64_t n, vr_stream_t stream);
 
 /*
  * Transposed bf16 shadows of a batch of fp32 matrices in one launch: for every descriptor d,

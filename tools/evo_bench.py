@@ -19,12 +19,14 @@ ap.add_argument("--candidates", type=int, default=16)
 ap.add_argument("--batches", type=int, default=8, help="validation batches of 256 images per candidate")
 ap.add_argument("--space", default="sr_small")
 ap.add_argument("--mac", type=float, default=2.9e9)
+ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "f32"], help="compute dtype of the scoring forwards")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 sp = getattr(supernet_config, args.space)
 model = vitres.create_model("flexible_vit_sr_patch14_224_patch_output_supernet", num_classes=1000, network_def=sp.network_def,
                             num_channels_to_keep=sp.num_channels_to_keep, example_per_arch=64, num_warmup_epochs=30)
-model = model.to(dev).set_compute_dtype(torch.bfloat16).eval()
+DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16, "f32": torch.float32}
+model = model.to(dev).set_compute_dtype(DTYPES[args.dtype]).eval()
 est = ComputationEstimator(distill=False, input_resolution=224, patch_size=14)
 rng = np.random.RandomState(0)
 cands, macs = [], []
@@ -44,7 +46,7 @@ scores = evo_eval.score_population(model, cands, batches)
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 imgs = len(cands) * len(batches) * 256
-print(json.dumps({"metric": "evo-eval candidates/s (C5, 1 GPU, resident sr_small supernet, bf16)", "candidates_per_s": round(len(cands) / dt, 3),
+print(json.dumps({"metric": "evo-eval candidates/s (C5, 1 GPU, resident sr_small supernet, %s)" % args.dtype, "candidates_per_s": round(len(cands) / dt, 3),
                   "images_per_s": round(imgs / dt, 1), "candidates": len(cands), "images_per_candidate": len(batches) * 256,
                   "mean_candidate_gmac": round(float(np.mean(macs)) / 1e9, 3),
                   "effective_tflops": round(2 * float(np.mean(macs)) * imgs / dt / 1e12, 1), "scores_head": scores[:3]}))

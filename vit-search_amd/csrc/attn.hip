@@ -13,13 +13,16 @@
 namespace vr_attn_mfma {   // attn_mfma.hip
 bool supported(int N, int H, int D);
 int fwd(const void* qkv, void* o, float* lse, const int* keep, int B, int N, int H, int D, float scale, hipStream_t st);
+int fwd_f16(const void* qkv, void* o, float* lse, const int* keep, int B, int N, int H, int D, float scale, hipStream_t st);
 int bwd(const void* qkv, const void* o, const void* d_o, const float* lse, float* delta, void* dqkv, const int* keep, int B,
         int N, int H, int D, float scale, hipStream_t st);
 }  // namespace vr_attn_mfma
 
 namespace {
 
-inline bool use_mfma(int dtype, int N, int H, int D) { return dtype == VR_BF16 && vr_attn_mfma::supported(N, H, D); }
+inline bool use_mfma(int dtype, int N, int H, int D) {
+    return (dtype == VR_BF16 || dtype == VR_F16) && vr_attn_mfma::supported(N, H, D);
+}
 
 constexpr int MAXT = 5;  // key groups of 64 per lane -> N <= 320
 
@@ -259,7 +262,8 @@ extern "C" int vr_attn_fwd(const void* qkv, void* o, float* lse, const int32_t* 
                            int32_t D, float scale, int32_t dtype, vr_stream_t stream) {
     if (!qkv || !o || !lse || B <= 0 || N <= 0 || H <= 0 || D <= 0) return VR_EINVAL;
     if (use_mfma(dtype, N, H, D)) {
-        const int rc = vr_attn_mfma::fwd(qkv, o, lse, keep_hd, B, N, H, D, scale, (hipStream_t)stream);
+        const int rc = dtype == VR_F16 ? vr_attn_mfma::fwd_f16(qkv, o, lse, keep_hd, B, N, H, D, scale, (hipStream_t)stream)
+                                       : vr_attn_mfma::fwd(qkv, o, lse, keep_hd, B, N, H, D, scale, (hipStream_t)stream);
         if (rc) return rc;
         VR_CHECK_LAUNCH();
         return VR_OK;
@@ -275,6 +279,10 @@ extern "C" int vr_attn_fwd(const void* qkv, void* o, float* lse, const int32_t* 
         if ((rc = set_lds(attn_fwd_kernel<bf16_t>, lds))) return rc;
         hipLaunchKernelGGL((attn_fwd_kernel<bf16_t>), dim3(B * H), dim3(256), lds, (hipStream_t)stream, (const bf16_t*)qkv,
                            (bf16_t*)o, lse, keep_hd, B, N, H, D, scale);
+    } else if (dtype == VR_F16) {
+        if ((rc = set_lds(attn_fwd_kernel<f16_t>, lds))) return rc;
+        hipLaunchKernelGGL((attn_fwd_kernel<f16_t>), dim3(B * H), dim3(256), lds, (hipStream_t)stream, (const f16_t*)qkv,
+                           (f16_t*)o, lse, keep_hd, B, N, H, D, scale);
     } else {
         return VR_EUNSUPPORTED;
     }
@@ -286,6 +294,7 @@ extern "C" int vr_attn_bwd(const void* qkv, const void* o, const void* d_o, cons
                            const int32_t* keep_hd, int32_t B, int32_t N, int32_t H, int32_t D, float scale, int32_t dtype,
                            vr_stream_t stream) {
     if (!qkv || !o || !d_o || !lse || !delta || !dqkv || B <= 0 || N <= 0 || H <= 0 || D <= 0) return VR_EINVAL;
+    if (dtype != VR_F32 && dtype != VR_BF16) return VR_EUNSUPPORTED;          // (fp16: forward only)
     if (use_mfma(dtype, N, H, D)) {
         const int rc = vr_attn_mfma::bwd(qkv, o, d_o, lse, delta, dqkv, keep_hd, B, N, H, D, scale, (hipStream_t)stream);
         if (rc) return rc;

@@ -34,9 +34,9 @@ template <int D> struct AC {
     static constexpr bool SWZ = (D != 48);
 };
 
-__device__ __forceinline__ f32x4 mfma16(bfv8 a, bfv8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
+// TI: element type of the operands (bf16_t; f16_t in the forward kernels of the fp16 mode).  The kernels stage and move both as raw
+// 16-bit lanes (bfv8 registers, bf16_t pointers); only the MFMA and the packing of P / O look at the encoding.
+template <typename TI = bf16_t> __device__ __forceinline__ f32x4 mfma16(bfv8 a, bfv8 b, f32x4 c) { return Half16<TI>::mfma16(a, b, c); }
 
 // ---- staging ---------------------------------------------------------------------------------------------
 // rows [N][D] at src (row stride rs elements) -> chunk-major LDS, rows N..Np-1 zero.
@@ -104,9 +104,9 @@ __device__ __forceinline__ bfv8 tfrag(const char* base, int Np, int kp, int dt, 
     const s8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bfv8, v);
 }
-__device__ __forceinline__ bfv8 pack8(const f32x4& a, const f32x4& b) {
-    return __builtin_bit_cast(bfv8, make_uint4(pack_bf2(a[0], a[1]), pack_bf2(a[2], a[3]), pack_bf2(b[0], b[1]),
-                                               pack_bf2(b[2], b[3])));
+template <typename TI = bf16_t> __device__ __forceinline__ bfv8 pack8(const f32x4& a, const f32x4& b) {
+    return __builtin_bit_cast(bfv8, make_uint4(Half16<TI>::pk(a[0], a[1]), Half16<TI>::pk(a[2], a[3]), Half16<TI>::pk(b[0], b[1]),
+                                               Half16<TI>::pk(b[2], b[3])));
 }
 __device__ __forceinline__ float gmax(float v) {   // over the 4 lanes sharing lane%16
     v = fmaxf(v, __shfl_xor(v, 16, 64));
@@ -173,7 +173,7 @@ template <int D, int NP> struct Img {
 // ==========================================================================================================
 // forward
 // ==========================================================================================================
-template <int D, int NKP, int NW, int PB, int OCC, bool FULL>
+template <int D, int NKP, int NW, int PB, int OCC, bool FULL, typename TI = bf16_t>
 __global__ __launch_bounds__(NW * 64, OCC) void fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
                                                            float* __restrict__ lse, const int* __restrict__ keep_hd, int B,
                                                            int N, int H, float scale, int ATTN_XCD) {
@@ -226,7 +226,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void fwd_kernel(const bf16_t* __restr
                     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
                     if (FULL || k0 < N) {
 #pragma unroll
-                        for (int dk = 0; dk < AC<D>::DK; ++dk) acc = mfma16(I::cread(kb[dk], k0), qf[dk], acc);
+                        for (int dk = 0; dk < AC<D>::DK; ++dk) acc = mfma16<TI>(I::cread(kb[dk], k0), qf[dk], acc);
                         // FULL: N > 32 (NKP - 1), only the last pair of tiles can hold rows >= N (compile-time choice of the
                         // masked tiles, no per-tile scalar conditions: those cost more SGPRs than the kernel has)
                         if (FULL ? (2 * b0 + j >= 2 * NKP - 2) : (k0 + 16 > N)) {
@@ -263,9 +263,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void fwd_kernel(const bf16_t* __restr
 #pragma unroll
                 for (int jp = 0; jp < PB; ++jp) {
                     if (FULL || (b0 + jp) * 32 < N) {
-                        const bfv8 pf = pack8(st[2 * jp], st[2 * jp + 1]);
+                        const bfv8 pf = pack8<TI>(st[2 * jp], st[2 * jp + 1]);
 #pragma unroll
-                        for (int dt = 0; dt < AC<D>::DT; ++dt) oacc[dt] = mfma16(I::tread(vb, b0 + jp, dt), pf, oacc[dt]);
+                        for (int dt = 0; dt < AC<D>::DT; ++dt) oacc[dt] = mfma16<TI>(I::tread(vb, b0 + jp, dt), pf, oacc[dt]);
                     }
                 }
                 // keep the blocks apart: in straight-line code the scheduler hoists every LDS read of the tile to the top and
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void fwd_kernel(const bf16_t* __restr
 #pragma unroll
             for (int dt = 0; dt < AC<D>::DT; ++dt)
                 *reinterpret_cast<uint2*>(ob + (long long)(qs + c) * HD + dt * 16 + 4 * g) =
-                    make_uint2(pack_bf2(oacc[dt][0] * inv, oacc[dt][1] * inv), pack_bf2(oacc[dt][2] * inv, oacc[dt][3] * inv));
+                    make_uint2(Half16<TI>::pk(oacc[dt][0] * inv, oacc[dt][1] * inv), Half16<TI>::pk(oacc[dt][2] * inv, oacc[dt][3] * inv));
             if (g == 0) lb[qs + c] = m * scale + __logf(sum);
         }
         if (q0 < N) {
@@ -776,7 +776,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_short_kernel(const bf16_t* _
 // ==========================================================================================================
 constexpr int LKB = 256, LQB = 128, LNW = 8;              // rows per staged block, rows per workgroup, waves
 
-template <int D>
+template <int D, typename TI = bf16_t>
 __global__ __launch_bounds__(LNW * 64) void fwd_long_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ o,
                                                             float* __restrict__ lse, const int* __restrict__ keep_hd, int B,
                                                             int N, int H, float scale) {
@@ -816,7 +816,7 @@ __global__ __launch_bounds__(LNW * 64) void fwd_long_kernel(const bf16_t* __rest
         for (int kt = 0; kt < LKB / 16; ++kt) {
             f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int dk = 0; dk < AC<D>::DK; ++dk) acc = mfma16(cfrag<D>(Kc, LKB, kt * 16, dk, lane), qf[dk], acc);
+            for (int dk = 0; dk < AC<D>::DK; ++dk) acc = mfma16<TI>(cfrag<D>(Kc, LKB, kt * 16, dk, lane), qf[dk], acc);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 acc[r] = (kt * 16 + 4 * g + r) < nk ? acc[r] * scale : -INFINITY;
@@ -854,21 +854,21 @@ __global__ __launch_bounds__(LNW * 64) void fwd_long_kernel(const bf16_t* __rest
                 const int kt = 2 * kp + tt;
                 f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int dk = 0; dk < AC<D>::DK; ++dk) acc = mfma16(cfrag<D>(Kc, LKB, kt * 16, dk, lane), qf[dk], acc);
+                for (int dk = 0; dk < AC<D>::DK; ++dk) acc = mfma16<TI>(cfrag<D>(Kc, LKB, kt * 16, dk, lane), qf[dk], acc);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) acc[r] = (kt * 16 + 4 * g + r) < nk ? __expf(acc[r] * scale - l) : 0.f;
                 pr[tt] = acc;
             }
-            const bfv8 pf = pack8(pr[0], pr[1]);
+            const bfv8 pf = pack8<TI>(pr[0], pr[1]);
 #pragma unroll
-            for (int dt = 0; dt < AC<D>::DT; ++dt) oacc[dt] = mfma16(tfrag<D>(Vc, LKB, kp, dt, lane), pf, oacc[dt]);
+            for (int dt = 0; dt < AC<D>::DT; ++dt) oacc[dt] = mfma16<TI>(tfrag<D>(Vc, LKB, kp, dt, lane), pf, oacc[dt]);
         }
     }
     if (q0 + c < N) {
 #pragma unroll
         for (int dt = 0; dt < AC<D>::DT; ++dt)
             *reinterpret_cast<uint2*>(ob + (long long)(q0 + c) * HD + dt * 16 + 4 * g) =
-                make_uint2(pack_bf2(oacc[dt][0], oacc[dt][1]), pack_bf2(oacc[dt][2], oacc[dt][3]));
+                make_uint2(Half16<TI>::pk(oacc[dt][0], oacc[dt][1]), Half16<TI>::pk(oacc[dt][2], oacc[dt][3]));
     }
 }
 
@@ -1075,21 +1075,21 @@ template <int NKP> struct Plan {
 
 // sample-major block order per XCD (common.h xcd_block)
 static constexpr int attn_xcd() { return 1; }
-template <int D, int NKP>
+template <int D, int NKP, typename TI = bf16_t>
 static int launch_fwd(const bf16_t* qkv, bf16_t* o, float* lse, const int* keep, int B, int N, int H, float scale,
                       hipStream_t st) {
     constexpr int NW = Plan<NKP>::NW, OCC = Plan<NKP>::OCC, PB = Plan<NKP>::PB;
     const size_t lds = (size_t)2 * Img<D, 32 * NKP>::BYTES;
     // FULL: the last pair of key tiles is in use (N = 257 / 65 / 17 and every N > 32 (NKP - 1)): no run-time tile guards
     if (N > 32 * (NKP - 1)) {
-        int rc = set_lds(fwd_kernel<D, NKP, NW, PB, OCC, true>, lds);
+        int rc = set_lds(fwd_kernel<D, NKP, NW, PB, OCC, true, TI>, lds);
         if (rc) return rc;
-        hipLaunchKernelGGL((fwd_kernel<D, NKP, NW, PB, OCC, true>), dim3(B * H), dim3(NW * 64), lds, st, qkv, o, lse, keep, B, N, H,
+        hipLaunchKernelGGL((fwd_kernel<D, NKP, NW, PB, OCC, true, TI>), dim3(B * H), dim3(NW * 64), lds, st, qkv, o, lse, keep, B, N, H,
                            scale, attn_xcd());
     } else {
-        int rc = set_lds(fwd_kernel<D, NKP, NW, PB, OCC, false>, lds);
+        int rc = set_lds(fwd_kernel<D, NKP, NW, PB, OCC, false, TI>, lds);
         if (rc) return rc;
-        hipLaunchKernelGGL((fwd_kernel<D, NKP, NW, PB, OCC, false>), dim3(B * H), dim3(NW * 64), lds, st, qkv, o, lse, keep, B, N, H,
+        hipLaunchKernelGGL((fwd_kernel<D, NKP, NW, PB, OCC, false, TI>), dim3(B * H), dim3(NW * 64), lds, st, qkv, o, lse, keep, B, N, H,
                            scale, attn_xcd());
     }
     return 0;
@@ -1142,13 +1142,13 @@ static int launch_bwd(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o, con
     return 0;
 }
 
-template <int D>
+template <int D, typename TI = bf16_t>
 static int launch_fwd_long(const bf16_t* qkv, bf16_t* o, float* lse, const int* keep, int B, int N, int H, float scale,
                            hipStream_t st) {
     const size_t lds = (size_t)2 * D * (LKB + 8) * 2;
-    int rc = set_lds(fwd_long_kernel<D>, lds);
+    int rc = set_lds(fwd_long_kernel<D, TI>, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL((fwd_long_kernel<D>), dim3(B * H * ((N + LQB - 1) / LQB)), dim3(LNW * 64), lds, st, qkv, o, lse, keep, B, N, H,
+    hipLaunchKernelGGL((fwd_long_kernel<D, TI>), dim3(B * H * ((N + LQB - 1) / LQB)), dim3(LNW * 64), lds, st, qkv, o, lse, keep, B, N, H,
                        scale);
     return 0;
 }
@@ -1186,6 +1186,21 @@ static int launch_bwd_long(const bf16_t* qkv, const bf16_t* o, const bf16_t* d_o
 
 bool supported(int N, int H, int D) {
     return (D == 32 || D == 48 || D == 64) && N >= 1 && ((H * D) % 8 == 0);
+}
+
+template <int D, int NKP>
+static int launch_fwd_h(const bf16_t* qkv, bf16_t* o, float* lse, const int* keep, int B, int N, int H, float scale, hipStream_t st) {
+    return launch_fwd<D, NKP, f16_t>(qkv, o, lse, keep, B, N, H, scale, st);
+}
+
+// fp16 forward (the evaluation mode of vr_attn_fwd): the same kernels and plans as bf16
+int fwd_f16(const void* qkv, void* o, float* lse, const int* keep, int B, int N, int H, int D, float scale, hipStream_t st) {
+    if (N > 288) {
+        if (D == 64) return launch_fwd_long<64, f16_t>((const bf16_t*)qkv, (bf16_t*)o, lse, keep, B, N, H, scale, st);
+        if (D == 48) return launch_fwd_long<48, f16_t>((const bf16_t*)qkv, (bf16_t*)o, lse, keep, B, N, H, scale, st);
+        return launch_fwd_long<32, f16_t>((const bf16_t*)qkv, (bf16_t*)o, lse, keep, B, N, H, scale, st);
+    }
+    VR_ATTN_DISPATCH(launch_fwd_h, (const bf16_t*)qkv, (bf16_t*)o, lse, keep, B, N, H, scale, st);
 }
 
 int fwd(const void* qkv, void* o, float* lse, const int* keep, int B, int N, int H, int D, float scale, hipStream_t st) {

@@ -5,6 +5,7 @@
 
 #define VR_F32 0
 #define VR_BF16 1
+#define VR_F16 2
 
 #define VR_OK 0
 #define VR_EINVAL (-1)
@@ -18,6 +19,10 @@
     } while (0)
 
 typedef uint16_t bf16_t;  // raw bf16 bits
+// raw IEEE binary16 bits: a struct, not a second uint16_t typedef, so that Elem<> / template dispatch tells it from bf16_t
+struct f16_t {
+    uint16_t bits;
+};
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -42,6 +47,47 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, vr_bf2));
 }
 
+// fp16 counterparts: v_cvt_f16_f32 / v_cvt_pk_f16_f32 round to nearest even (never the pkrtz form, which truncates); overflow
+// gives +-inf and NaN stays NaN -- torch's .half()
+typedef _Float16 vr_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float h2f(f16_t h) { return (float)__builtin_bit_cast(_Float16, h.bits); }
+__device__ __forceinline__ f16_t f2h(float f) { return f16_t{__builtin_bit_cast(uint16_t, (_Float16)f)}; }
+__device__ __forceinline__ uint32_t pack_h2(float lo, float hi) {
+    const vr_f2 v = {lo, hi};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, vr_h2));
+}
+
+// 16-bit element types of the MFMA kernels: pack / unpack of a dword holding two elements (low half first) and the MFMAs
+// (operands as raw 16-bit lanes: the kernels stage both types with the same loads)
+typedef short vr_s8 __attribute__((ext_vector_type(8)));
+typedef __bf16 vr_bf8 __attribute__((ext_vector_type(8)));
+typedef _Float16 vr_h8 __attribute__((ext_vector_type(8)));
+template <typename T> struct Half16;
+template <> struct Half16<bf16_t> {
+    static constexpr int dtype = VR_BF16;
+    __device__ static __forceinline__ uint32_t pk(float lo, float hi) { return pack_bf2(lo, hi); }
+    __device__ static __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
+    __device__ static __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+    template <typename V> __device__ static __forceinline__ f32x4 mfma16(V a, V b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(vr_bf8, a), __builtin_bit_cast(vr_bf8, b), c, 0, 0, 0);
+    }
+    template <typename V> __device__ static __forceinline__ f32x16 mfma32(V a, V b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(vr_bf8, a), __builtin_bit_cast(vr_bf8, b), c, 0, 0, 0);
+    }
+};
+template <> struct Half16<f16_t> {
+    static constexpr int dtype = VR_F16;
+    __device__ static __forceinline__ uint32_t pk(float lo, float hi) { return pack_h2(lo, hi); }
+    __device__ static __forceinline__ float lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu)); }
+    __device__ static __forceinline__ float hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
+    template <typename V> __device__ static __forceinline__ f32x4 mfma16(V a, V b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(vr_h8, a), __builtin_bit_cast(vr_h8, b), c, 0, 0, 0);
+    }
+    template <typename V> __device__ static __forceinline__ f32x16 mfma32(V a, V b, f32x16 c) {
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(vr_h8, a), __builtin_bit_cast(vr_h8, b), c, 0, 0, 0);
+    }
+};
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
     static constexpr int dtype = VR_F32;
@@ -52,6 +98,11 @@ template <> struct Elem<bf16_t> {
     static constexpr int dtype = VR_BF16;
     __device__ static __forceinline__ float ld(const bf16_t* p) { return bf2f(*p); }
     __device__ static __forceinline__ void st(bf16_t* p, float v) { *p = f2bf(v); }
+};
+template <> struct Elem<f16_t> {
+    static constexpr int dtype = VR_F16;
+    __device__ static __forceinline__ float ld(const f16_t* p) { return h2f(*p); }
+    __device__ static __forceinline__ void st(f16_t* p, float v) { *p = f2h(v); }
 };
 
 // XCD-contiguous block order (round 4): workgroups go to the eight XCDs round-robin (block b -> XCD b % 8); xcd_block() gives

@@ -10,6 +10,8 @@
 //   computed transposed (weights first): a lane owns one pixel and 4 consecutive output channels -> 16-byte stores.
 // The pixel stride in LDS is Cin*2 bytes, padded by 16 when Cin/8 is even, so the 16 pixels of a fragment read hit 16
 // different 16-byte slots.
+#include <type_traits>
+
 #include "common.h"
 #include "../../include/vitres_hip.h"
 
@@ -18,7 +20,8 @@ namespace {
 typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
 constexpr int TH = 16, TW = 16, PH = TH + 2, PW = TW + 2;
 
-template <int NC, typename TO>
+// TI: operand type (bf16_t; f16_t for the fp16 evaluation stem -- a / w / res are raw 16-bit lanes either way)
+template <int NC, typename TO, typename TI = bf16_t>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ w,
                                                       TO* __restrict__ out, int B, int H, int W, int Cout,
                                                       const float* __restrict__ bias, const bf16_t* __restrict__ res, int psz, int rpsz) {
@@ -77,8 +80,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
 #pragma unroll
         for (int ks = 0; ks < STEPS; ++ks) {
             const bfv8 af = *reinterpret_cast<const bfv8*>(base + koff[ks]);
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][0], af, acc0, 0, 0, 0);
-            if (nt1) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][1], af, acc1, 0, 0, 0);
+            acc0 = Half16<TI>::mfma16(wf[ks][0], af, acc0);
+            if (nt1) acc1 = Half16<TI>::mfma16(wf[ks][1], af, acc1);
         }
         const int oy = y0 + r, ox = x0 + c;
         if (oy < H && ox < W) {
@@ -103,11 +106,11 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
                         if (rpsz > 0)
                             rpix = (((long long)b * (H / rpsz) + oy / rpsz) * (W / rpsz) + ox / rpsz) * (rpsz * rpsz) + (oy % rpsz) * rpsz + ox % rpsz;
                         const uint2 rr = *reinterpret_cast<const uint2*>(res + rpix * Cout + co);
-                        r4[0] += __uint_as_float(rr.x << 16); r4[1] += __uint_as_float(rr.x & 0xffff0000u);
-                        r4[2] += __uint_as_float(rr.y << 16); r4[3] += __uint_as_float(rr.y & 0xffff0000u);
+                        r4[0] += Half16<TI>::lo(rr.x); r4[1] += Half16<TI>::hi(rr.x);
+                        r4[2] += Half16<TI>::lo(rr.y); r4[3] += Half16<TI>::hi(rr.y);
                     }
                     if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(dst + co) = make_float4(r4[0], r4[1], r4[2], r4[3]);
-                    else *reinterpret_cast<uint2*>(dst + co) = make_uint2(pack_bf2(r4[0], r4[1]), pack_bf2(r4[2], r4[3]));
+                    else *reinterpret_cast<uint2*>(dst + co) = make_uint2(Half16<TO>::pk(r4[0], r4[1]), Half16<TO>::pk(r4[2], r4[3]));
                 }
             }
         }
@@ -122,7 +125,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
 // consecutive output channels.  Optional epilogue (evaluation, BatchNorm folded into w): relu(. + bias).
 constexpr int C1_TH = 8, C1_TW = 32, C1_IH = 2 * C1_TH + 1, C1_IW = 2 * C1_TW + 1, C1_IWP = C1_IW + 1;
 
-template <typename TO>
+// TI: type of w and of the staged image (bf16_t; f16_t for the fp16 evaluation stem)
+template <typename TO, typename TI = bf16_t>
 __global__ __launch_bounds__(256) void conv1_direct_kernel(const float* __restrict__ img, const bf16_t* __restrict__ w,
                                                            const float* __restrict__ bias, TO* __restrict__ out, int B, int H, int W,
                                                            int Ho, int Wo, int Cout, int relu) {
@@ -138,7 +142,8 @@ __global__ __launch_bounds__(256) void conv1_direct_kernel(const float* __restri
         const int y = rem / C1_IW, x = rem - y * C1_IW;
         const int iy = iy0 + y, ix = ix0 + x;
         const float v = (iy >= 0 && iy < H && ix >= 0 && ix < W) ? src[((long long)ch * H + iy) * W + ix] : 0.f;
-        patch[(ch * C1_IH + y) * C1_IWP + x] = f2bf(v);
+        if constexpr (std::is_same_v<TI, f16_t>) patch[(ch * C1_IH + y) * C1_IWP + x] = f2h(v).bits;
+        else patch[(ch * C1_IH + y) * C1_IWP + x] = f2bf(v);
     }
     // weight fragments: channel 16 nf + c, k = 8 g .. 8 g + 7
     bfv8 wf[2];
@@ -173,8 +178,8 @@ __global__ __launch_bounds__(256) void conv1_direct_kernel(const float* __restri
                                         (unsigned)e[4] | ((unsigned)e[5] << 16), (unsigned)e[6] | ((unsigned)e[7] << 16));
             const bfv8 af = __builtin_bit_cast(bfv8, av);
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[0], af, acc0, 0, 0, 0);
-            if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[1], af, acc1, 0, 0, 0);
+            acc0 = Half16<TI>::mfma16(wf[0], af, acc0);
+            if (two) acc1 = Half16<TI>::mfma16(wf[1], af, acc1);
             const int oy = oy0 + oyl, ox = ox0 + oxl;
             if (oy < Ho && ox < Wo) {
                 TO* dst = out + (((long long)b * Ho + oy) * Wo + ox) * Cout;
@@ -189,7 +194,7 @@ __global__ __launch_bounds__(256) void conv1_direct_kernel(const float* __restri
                         }
                         if (relu) { r4[0] = fmaxf(r4[0], 0.f); r4[1] = fmaxf(r4[1], 0.f); r4[2] = fmaxf(r4[2], 0.f); r4[3] = fmaxf(r4[3], 0.f); }
                         if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(dst + co) = make_float4(r4[0], r4[1], r4[2], r4[3]);
-                        else *reinterpret_cast<uint2*>(dst + co) = make_uint2(pack_bf2(r4[0], r4[1]), pack_bf2(r4[2], r4[3]));
+                        else *reinterpret_cast<uint2*>(dst + co) = make_uint2(Half16<TO>::pk(r4[0], r4[1]), Half16<TO>::pk(r4[2], r4[3]));
                     }
                 }
             }
@@ -314,6 +319,8 @@ template <int NC> int launch(const bf16_t* a, const bf16_t* w, void* out, int B,
                              const float* bias = nullptr, const bf16_t* res = nullptr, int patch = 0, int rpatch = 0) {
     const unsigned grid = (unsigned)(B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW));
     if (out_dtype == VR_F32) hipLaunchKernelGGL((conv3x3_kernel<NC, float>), dim3(grid), dim3(256), 0, st, a, w, (float*)out, B, H, W, Cout, bias, res, patch, rpatch);
+    else if (out_dtype == VR_F16)     // (fp16 operands: the fp16 forms have a 16-bit result)
+        hipLaunchKernelGGL((conv3x3_kernel<NC, f16_t, f16_t>), dim3(grid), dim3(256), 0, st, a, w, (f16_t*)out, B, H, W, Cout, bias, res, patch, rpatch);
     else hipLaunchKernelGGL((conv3x3_kernel<NC, bf16_t>), dim3(grid), dim3(256), 0, st, a, w, (bf16_t*)out, B, H, W, Cout, bias, res, patch, rpatch);
     return 0;
 }
@@ -375,7 +382,7 @@ extern "C" int vr_conv3x3_bias_relu_patch(const void* a, const void* w, const fl
 static int conv3x3_entry(const void* a, const void* w, void* out, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                          int32_t out_dtype, const float* bias, const void* res, vr_stream_t stream, int patch, int rpatch) {
     if (!a || !w || !out || B <= 0 || H <= 0 || W <= 0) return VR_EINVAL;
-    if (out_dtype != VR_F32 && out_dtype != VR_BF16) return VR_EUNSUPPORTED;
+    if (out_dtype != VR_F32 && out_dtype != VR_BF16 && out_dtype != VR_F16) return VR_EUNSUPPORTED;
     if (Cout <= 0 || Cout > 32 || Cout % 4) return VR_EUNSUPPORTED;
     if (((uintptr_t)a & 15) || ((uintptr_t)w & 15) || ((uintptr_t)out & 15)) return VR_EALIGN;
     hipStream_t st = (hipStream_t)stream;
@@ -392,7 +399,7 @@ static int conv3x3_entry(const void* a, const void* w, void* out, int32_t B, int
 extern "C" int vr_conv1_direct(const float* img, const void* w, const float* bias, void* out, int32_t B, int32_t H, int32_t W,
                                int32_t Cout, int32_t relu, int32_t out_dtype, vr_stream_t stream) {
     if (!img || !w || !out || B <= 0 || H <= 0 || W <= 0) return VR_EINVAL;
-    if (out_dtype != VR_F32 && out_dtype != VR_BF16) return VR_EUNSUPPORTED;
+    if (out_dtype != VR_F32 && out_dtype != VR_BF16 && out_dtype != VR_F16) return VR_EUNSUPPORTED;
     if (Cout <= 0 || Cout > 32 || Cout % 4) return VR_EUNSUPPORTED;
     if (((uintptr_t)w & 15) || ((uintptr_t)out & 15) || (bias && ((uintptr_t)bias & 15))) return VR_EALIGN;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
@@ -401,6 +408,9 @@ extern "C" int vr_conv1_direct(const float* img, const void* w, const float* bia
     if (out_dtype == VR_F32)
         hipLaunchKernelGGL((conv1_direct_kernel<float>), dim3(grid), dim3(256), 0, st, img, (const bf16_t*)w, bias, (float*)out, B, H, W,
                            Ho, Wo, Cout, relu);
+    else if (out_dtype == VR_F16)     // (fp16 weights: the fp16 form has a 16-bit result)
+        hipLaunchKernelGGL((conv1_direct_kernel<f16_t, f16_t>), dim3(grid), dim3(256), 0, st, img, (const bf16_t*)w, bias, (f16_t*)out, B, H,
+                           W, Ho, Wo, Cout, relu);
     else
         hipLaunchKernelGGL((conv1_direct_kernel<bf16_t>), dim3(grid), dim3(256), 0, st, img, (const bf16_t*)w, bias, (bf16_t*)out, B, H,
                            W, Ho, Wo, Cout, relu);

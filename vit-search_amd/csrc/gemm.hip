@@ -50,6 +50,7 @@ template <> struct Cfg<bf16_t> {
     static constexpr int BK = 64;  // elements per K slice
     static constexpr int EPC = 8;  // elements per 16-B chunk
 };
+template <> struct Cfg<f16_t> : Cfg<bf16_t> {};      // (fp16: the forward forms, K-contiguous operands only)
 template <> struct Cfg<float> {
     static constexpr int BK = 32;
     static constexpr int EPC = 4;
@@ -225,9 +226,9 @@ template <int ROWS, int NTHR> struct LoaderT<float, ROWS, NTHR> {
 };
 
 // ---- LDS -> MFMA (SWAP: transposed tile, first operand = B fragment) ------------------------------------------
-template <bool SWAP, int MI, int NI>
+template <bool SWAP, int MI, int NI, typename T16>
 __device__ __forceinline__ void mma_tile(f32x16 (&acc)[MI][NI], const char* As, const char* Bs, int wm, int wn, int lane,
-                                         bf16_t*) {
+                                         T16*) {
     typedef __bf16 bfv8 __attribute__((ext_vector_type(8)));
     const int rr = lane & 31, kh = lane >> 5;
 #pragma unroll
@@ -243,8 +244,7 @@ __device__ __forceinline__ void mma_tile(f32x16 (&acc)[MI][NI], const char* As, 
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int j = 0; j < NI; ++j)
-                acc[i][j] = SWAP ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0)
-                                 : __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
+                acc[i][j] = SWAP ? Half16<T16>::mfma32(b[j], a[i], acc[i][j]) : Half16<T16>::mfma32(a[i], b[j], acc[i][j]);
     }
 }
 template <bool SWAP, int MI, int NI>
@@ -275,7 +275,7 @@ template <typename TO> __device__ __forceinline__ void store4(void* base, long l
     TO* p = reinterpret_cast<TO*>(base) + idx;
     if (vec) {
         if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-        else *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+        else *reinterpret_cast<uint2*>(p) = make_uint2(Half16<TO>::pk(v[0], v[1]), Half16<TO>::pk(v[2], v[3]));
     } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -291,8 +291,8 @@ template <typename TI> __device__ __forceinline__ void load4(const void* base, l
             v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
         } else {
             const uint2 u = *reinterpret_cast<const uint2*>(p);
-            v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-            v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
+            v[0] = Half16<TI>::lo(u.x); v[1] = Half16<TI>::hi(u.x);
+            v[2] = Half16<TI>::lo(u.y); v[3] = Half16<TI>::hi(u.y);
         }
     } else {
 #pragma unroll
@@ -729,24 +729,32 @@ void launch1(vr_gemm_args a, hipStream_t stream) {
 template <typename T>
 int launch(const vr_gemm_args& a, hipStream_t stream) {
     const bool of32 = a.out_dtype == VR_F32;
+    typedef typename std::conditional<sizeof(T) == 4, bf16_t, T>::type T16;     // 16-bit result type
+    if constexpr (std::is_same<T, f16_t>::value) {                                // fp16: the forward forms (no backward exists)
+        if (a.atomic || a.a_trans || a.b_trans || a.dact_u) return VR_EUNSUPPORTED;
+    }
     if (a.atomic) {                                             // weight gradients (fp32 accumulate)
-        if (a.a_trans && a.b_trans) launch1<T, true, true, float, EPI_ATOMIC>(a, stream);
-        else return VR_EUNSUPPORTED;
+        if constexpr (!std::is_same<T, f16_t>::value) {
+            if (a.a_trans && a.b_trans) launch1<T, true, true, float, EPI_ATOMIC>(a, stream);
+            else return VR_EUNSUPPORTED;
+        }
     } else if (a.a_trans) {
         return VR_EUNSUPPORTED;
     } else if (a.act == 1 || a.act == 3 || (a.act == 2 && !a.dact_u)) {
         if (a.b_trans || of32 != (sizeof(T) == 4)) return VR_EUNSUPPORTED;
         launch1<T, false, false, T, EPI_GELU>(a, stream);
     } else if (a.dact_u) {
-        if (of32 != (sizeof(T) == 4)) return VR_EUNSUPPORTED;
-        if (a.b_trans) launch1<T, false, true, T, EPI_DGELU>(a, stream);
-        else launch1<T, false, false, T, EPI_DGELU>(a, stream);
+        if constexpr (!std::is_same<T, f16_t>::value) {
+            if (of32 != (sizeof(T) == 4)) return VR_EUNSUPPORTED;
+            if (a.b_trans) launch1<T, false, true, T, EPI_DGELU>(a, stream);
+            else launch1<T, false, false, T, EPI_DGELU>(a, stream);
+        }
     } else if (!a.b_trans) {
         if (of32) launch1<T, false, false, float, EPI_STORE>(a, stream);
-        else launch1<T, false, false, bf16_t, EPI_STORE>(a, stream);
-    } else {
+        else launch1<T, false, false, T16, EPI_STORE>(a, stream);
+    } else if constexpr (!std::is_same<T, f16_t>::value) {
         if (of32) launch1<T, false, true, float, EPI_STORE>(a, stream);
-        else launch1<T, false, true, bf16_t, EPI_STORE>(a, stream);
+        else launch1<T, false, true, T16, EPI_STORE>(a, stream);
     }
     VR_CHECK_LAUNCH();
     return VR_OK;
@@ -767,10 +775,12 @@ static int gemm_validate(vr_gemm_args& a) {
     if (a.atomic && a.out_dtype != VR_F32) return VR_EINVAL;
     if (a.bias_grad && !(a.a_trans && a.atomic)) return VR_EINVAL;
     if (a.act < 0 || a.act > 3 || (a.act == 3 && (a.C2 || a.dact_u))) return VR_EINVAL;
-    if (a.in_dtype != VR_F32 && a.in_dtype != VR_BF16) return VR_EUNSUPPORTED;
-    if (a.out_dtype != VR_F32 && a.out_dtype != VR_BF16) return VR_EUNSUPPORTED;
-    const int epc = a.in_dtype == VR_BF16 ? 8 : 4;
-    const int esz = a.in_dtype == VR_BF16 ? 2 : 4;
+    if (a.in_dtype != VR_F32 && a.in_dtype != VR_BF16 && a.in_dtype != VR_F16) return VR_EUNSUPPORTED;
+    if (a.out_dtype != VR_F32 && a.out_dtype != VR_BF16 && a.out_dtype != VR_F16) return VR_EUNSUPPORTED;
+    // fp16 in with fp32 or fp16 out; bf16 and fp16 never mix
+    if ((a.in_dtype == VR_F16) != (a.out_dtype == VR_F16) && a.out_dtype != VR_F32) return VR_EUNSUPPORTED;
+    const int epc = a.in_dtype == VR_F32 ? 4 : 8;
+    const int esz = a.in_dtype == VR_F32 ? 4 : 2;
     // K-contiguous operands are fetched in 16-byte chunks (rows must be readable up to roundup(K, chunk): the caller
     // zero-pads); contraction-major ones in dwords.  Offsets are 32-bit: operands must be < 4 GiB.
     const int kpad = (a.K + epc - 1) / epc * epc;
@@ -789,7 +799,9 @@ static int gemm_validate(vr_gemm_args& a) {
         (a.bias && ((uintptr_t)a.bias & 15)) || (a.pos && ((uintptr_t)a.pos & 15)) ||
         (a.dact_u && ((uintptr_t)a.dact_u & 15)))
         return VR_EALIGN;
-    if (a.in_dtype == VR_F32 && a.out_dtype == VR_BF16) return VR_EUNSUPPORTED;
+    if (a.in_dtype == VR_F32 && a.out_dtype != VR_F32) return VR_EUNSUPPORTED;
+    // the opt-in forms (K-split shares, panel-resident kernel: sched 0x200000) exist in bf16 only
+    if (a.in_dtype == VR_F16 && (a.k_shares > 1 || (a.sched & 0x200000))) return VR_EUNSUPPORTED;
     if (a.ws && (((uintptr_t)a.ws & 15) || a.ws_bytes < 0)) return VR_EALIGN;
     return VR_OK;
 }
@@ -814,6 +826,7 @@ extern "C" int vr_gemm(const vr_gemm_args* args, vr_stream_t stream) {
     // sched bit 0x80000 (masked tiles of the operands may be unwritten): only the group-pure bf16 kernels may read them
     if ((a.sched & 0x80000) && a.m_groups > 1 && (a.keep_k || (a.a_trans && a.keep_n))) return VR_EUNSUPPORTED;
     if (a.in_dtype == VR_BF16) return launch<bf16_t>(a, (hipStream_t)stream);
+    if (a.in_dtype == VR_F16) return launch<f16_t>(a, (hipStream_t)stream);
     return launch<float>(a, (hipStream_t)stream);
 }
 

@@ -24,6 +24,8 @@
 // with the same shape, all loads of a round before its first store (vmcnt counts stores).
 #include <cstdlib>
 
+#include <type_traits>
+
 #include "gemm_nt_parts.h"
 
 namespace vr_gemm_nt {
@@ -48,7 +50,8 @@ __device__ const uint4 zero_chunk[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}
                 (long long)wall_clock64() * 16 + (slot);                                                 \
     } while (0)
 
-template <typename TO, int EPI, bool FAST, int MI, int NJ, int STAGES, int FEAT, bool BKM = false>
+// TI: 16-bit operand type (bf16_t; f16_t for the forward forms of the fp16 mode)
+template <typename TI, typename TO, int EPI, bool FAST, int MI, int NJ, int STAGES, int FEAT, bool BKM = false>
 __global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm_args p) {
     constexpr int BM = 32 * MI, WROWS = 16 * MI;      // tile rows, rows per wave
     constexpr int BN = 32 * NJ, WCOLS = 16 * NJ;      // tile columns, columns per wave
@@ -215,7 +218,7 @@ __global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = Half16<TI>::mfma16(b[j], a[i], acc[i][j]);
         }
     };
     auto fill_rowmeta = [&]() {      // per-row epilogue metadata (its loads overlap the first slices)
@@ -315,17 +318,17 @@ __global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm
     NT_STAMP(5);
 }
 
-template <typename TO, int EPI, int MI, int NJ, int STAGES, int FEAT> void launch3(const vr_gemm_args& a, hipStream_t stream, bool fast) {
+template <typename TI, typename TO, int EPI, int MI, int NJ, int STAGES, int FEAT> void launch3(const vr_gemm_args& a, hipStream_t stream, bool fast) {
     const long long total = (long long)((a.M + 32 * MI - 1) / (32 * MI)) * ((a.N + 32 * NJ - 1) / (32 * NJ));
-    if (fast) hipLaunchKernelGGL((nt_kernel<TO, EPI, true, MI, NJ, STAGES, FEAT>), dim3((unsigned)total), dim3(NTHR), 0, stream, a);
-    else hipLaunchKernelGGL((nt_kernel<TO, EPI, false, MI, NJ, STAGES, 4>), dim3((unsigned)total), dim3(NTHR), 0, stream, a);
+    if (fast) hipLaunchKernelGGL((nt_kernel<TI, TO, EPI, true, MI, NJ, STAGES, FEAT>), dim3((unsigned)total), dim3(NTHR), 0, stream, a);
+    else hipLaunchKernelGGL((nt_kernel<TI, TO, EPI, false, MI, NJ, STAGES, 4>), dim3((unsigned)total), dim3(NTHR), 0, stream, a);
 }
 
-template <typename TO, int EPI, int MI, int NJ, int STAGES = 1> void launch2(const vr_gemm_args& a, hipStream_t stream, bool fast) {
+template <typename TI, typename TO, int EPI, int MI, int NJ, int STAGES = 1> void launch2(const vr_gemm_args& a, hipStream_t stream, bool fast) {
     if (a.b_trans) {     // weights as the forward stores them (vr_gemm_nt_launch admitted the form): bf16 data gradients only
-        if constexpr (sizeof(TO) == 2 && (EPI == EPI_STORE || EPI == EPI_DMUL || EPI == EPI_DGELU)) {
+        if constexpr (std::is_same_v<TI, bf16_t> && sizeof(TO) == 2 && (EPI == EPI_STORE || EPI == EPI_DMUL || EPI == EPI_DGELU)) {
             const long long total = (long long)((a.M + 32 * MI - 1) / (32 * MI)) * ((a.N + 32 * NJ - 1) / (32 * NJ));
-            hipLaunchKernelGGL((nt_kernel<TO, EPI, true, MI, NJ, STAGES, 0, true>), dim3((unsigned)total), dim3(NTHR), 0, stream, a);
+            hipLaunchKernelGGL((nt_kernel<TI, TO, EPI, true, MI, NJ, STAGES, 0, true>), dim3((unsigned)total), dim3(NTHR), 0, stream, a);
         }
         return;
     }
@@ -339,42 +342,42 @@ template <typename TO, int EPI, int MI, int NJ, int STAGES = 1> void launch2(con
     }
     if constexpr (EPI == EPI_STORE) {
         switch (feat) {
-            case 0: return launch3<TO, EPI, MI, NJ, STAGES, 0>(a, stream, fast);
-            case 1: return launch3<TO, EPI, MI, NJ, STAGES, 1>(a, stream, fast);
-            case 2: return launch3<TO, EPI, MI, NJ, STAGES, 2>(a, stream, fast);
-            case 3: return launch3<TO, EPI, MI, NJ, STAGES, 3>(a, stream, fast);
-            default: return launch3<TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
+            case 0: return launch3<TI, TO, EPI, MI, NJ, STAGES, 0>(a, stream, fast);
+            case 1: return launch3<TI, TO, EPI, MI, NJ, STAGES, 1>(a, stream, fast);
+            case 2: return launch3<TI, TO, EPI, MI, NJ, STAGES, 2>(a, stream, fast);
+            case 3: return launch3<TI, TO, EPI, MI, NJ, STAGES, 3>(a, stream, fast);
+            default: return launch3<TI, TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
         }
     } else if constexpr (EPI == EPI_GELU) {
-        if (feat == 1) return launch3<TO, EPI, MI, NJ, STAGES, 1>(a, stream, fast);
-        if (feat == 0) return launch3<TO, EPI, MI, NJ, STAGES, 0>(a, stream, fast);
-        return launch3<TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
+        if (feat == 1) return launch3<TI, TO, EPI, MI, NJ, STAGES, 1>(a, stream, fast);
+        if (feat == 0) return launch3<TI, TO, EPI, MI, NJ, STAGES, 0>(a, stream, fast);
+        return launch3<TI, TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
     } else {
-        if (feat == 0) return launch3<TO, EPI, MI, NJ, STAGES, 0>(a, stream, fast);
-        return launch3<TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
+        if (feat == 0) return launch3<TI, TO, EPI, MI, NJ, STAGES, 0>(a, stream, fast);
+        return launch3<TI, TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
     }
 }
 
-template <typename TO, int EPI> void launch1(const vr_gemm_args& a, hipStream_t stream, int n_cu) {
+template <typename TI, typename TO, int EPI> void launch1(const vr_gemm_args& a, hipStream_t stream, int n_cu) {
     const long long tn = (a.N + 127) / 128;
     const long long t128 = (long long)((a.M + 127) / 128) * tn, t64 = (long long)((a.M + 63) / 64) * tn;
     const bool fast = a.N % 8 == 0 && a.ldc % 8 == 0 && (!a.dact_u || a.ldu % 8 == 0) && (a.n_period <= 0 || a.n_period % 8 == 0);
     // tile by grid size (measured crossovers, tools/gemm_bench.py): 128x128 while it gives a CU two workgroups, 64x128
     // below that, 64x64 when even that leaves CUs with a single workgroup (long-K GEMMs of the last stage)
     const int tile = t128 >= 2LL * n_cu ? 1 : (t64 >= 2LL * n_cu ? 2 : 3);
-    if (tile == 1) launch2<TO, EPI, 4, 4>(a, stream, fast);
+    if (tile == 1) launch2<TI, TO, EPI, 4, 4>(a, stream, fast);
     else if (tile == 2) {
         // every tile resident at three workgroups per CU and >= 8 slices: two slices per round (STAGES = 2)
-        if (t64 <= 3LL * n_cu && a.K >= 8 * BK) launch2<TO, EPI, 2, 4, 2>(a, stream, fast);
-        else launch2<TO, EPI, 2, 4>(a, stream, fast);
+        if (t64 <= 3LL * n_cu && a.K >= 8 * BK) launch2<TI, TO, EPI, 2, 4, 2>(a, stream, fast);
+        else launch2<TI, TO, EPI, 2, 4>(a, stream, fast);
     } else {
         // 64 x 64 tiles: with fewer than ~3 workgroups per CU and a long K the slices are pipelined inside the workgroup
         const long long t3 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
         const bool ring = t3 < 3LL * n_cu && a.K >= 24 * BK;      // measured: +23 % at K = 3072, -3 % at K = 1024
-        if (ring) launch2<TO, EPI, 2, 2, 3>(a, stream, fast);
-        else if (t3 <= n_cu && a.K >= 4 * BK) launch2<TO, EPI, 2, 2, 4>(a, stream, fast);   // at most one workgroup per CU
-        else if (a.K >= 8 * BK) launch2<TO, EPI, 2, 2, 2>(a, stream, fast);
-        else launch2<TO, EPI, 2, 2>(a, stream, fast);
+        if (ring) launch2<TI, TO, EPI, 2, 2, 3>(a, stream, fast);
+        else if (t3 <= n_cu && a.K >= 4 * BK) launch2<TI, TO, EPI, 2, 2, 4>(a, stream, fast);   // at most one workgroup per CU
+        else if (a.K >= 8 * BK) launch2<TI, TO, EPI, 2, 2, 2>(a, stream, fast);
+        else launch2<TI, TO, EPI, 2, 2>(a, stream, fast);
     }
 }
 
@@ -385,7 +388,9 @@ bool vr_gemm_ntk_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu, con
 // Called by vr_gemm after validation.  Returns false when the form is not covered here.
 bool vr_gemm_nt_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu) {
     using namespace vr_gemm_nt;
-    if (a.in_dtype != VR_BF16 || a.a_trans || a.atomic || a.split_k > 1 || a.bias_grad) return false;
+    const bool f16 = a.in_dtype == VR_F16;
+    if ((a.in_dtype != VR_BF16 && !f16) || a.a_trans || a.atomic || a.split_k > 1 || a.bias_grad) return false;
+    if (f16 && (a.b_trans || a.dact_u)) return false;                  // fp16: the forward forms only
     if (vr_gemm_ntk_launch(a, stream, n_cu, nullptr)) return true;
     // sched bit 0x80000: the operand may hold unwritten (fully masked) tiles, readable only by the group-pure row tiling of
     // gemm_ntk.hip -- the kernels below tile across architecture groups: refused (vr_gemm then fails loudly)
@@ -401,15 +406,18 @@ bool vr_gemm_nt_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu) {
     }
     if (a.act == 1 || a.act == 3 || (a.act == 2 && !a.dact_u)) {
         if (of32) return false;
-        launch1<bf16_t, EPI_GELU>(a, stream, n_cu);
+        if (f16) launch1<f16_t, f16_t, EPI_GELU>(a, stream, n_cu);
+        else launch1<bf16_t, bf16_t, EPI_GELU>(a, stream, n_cu);
     } else if (a.dact_u) {
         if (of32) return false;
-        if (a.act == 2) launch1<bf16_t, EPI_DMUL>(a, stream, n_cu);
-        else launch1<bf16_t, EPI_DGELU>(a, stream, n_cu);
+        if (a.act == 2) launch1<bf16_t, bf16_t, EPI_DMUL>(a, stream, n_cu);
+        else launch1<bf16_t, bf16_t, EPI_DGELU>(a, stream, n_cu);
     } else if (of32) {
-        launch1<float, EPI_STORE>(a, stream, n_cu);
+        if (f16) launch1<f16_t, float, EPI_STORE>(a, stream, n_cu);
+        else launch1<bf16_t, float, EPI_STORE>(a, stream, n_cu);
     } else {
-        launch1<bf16_t, EPI_STORE>(a, stream, n_cu);
+        if (f16) launch1<f16_t, f16_t, EPI_STORE>(a, stream, n_cu);
+        else launch1<bf16_t, bf16_t, EPI_STORE>(a, stream, n_cu);
     }
     return true;
 }

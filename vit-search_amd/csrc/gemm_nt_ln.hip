@@ -46,7 +46,8 @@ struct RowMeta {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-template <int MI, int NJ, int MODE, bool KTAIL>
+// TI: 16-bit operand type -- bf16_t, or f16_t for the forward (MODE 0, y written in fp16) of the fp16 mode
+template <typename TI, int MI, int NJ, int MODE, bool KTAIL>
 __global__ __launch_bounds__(NTHR, NJ > 5 ? 2 : 3) void ntln_kernel(   // (32 x 512 tiles: 68 KB of LDS, two per CU)
    const vr_gemm_args p, const vr_ln_epilogue f) {
     constexpr int BM = 16 * MI, BN = 64 * NJ, WCOLS = 16 * NJ;
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(NTHR, NJ > 5 ? 2 : 3) void ntln_kernel(   // (32 x 
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = Half16<TI>::mfma16(b[j], a[i], acc[i][j]);
         }
     };
 
@@ -325,8 +326,8 @@ __global__ __launch_bounds__(NTHR, NJ > 5 ? 2 : 3) void ntln_kernel(   // (32 x 
                                 const float o1 = (1 < kl) ? lw[v].y * ((x1[v].y - mu) * rs) + lb[v].y : 0.f;
                                 const float o2 = (2 < kl) ? lw[v].z * ((x1[v].z - mu) * rs) + lb[v].z : 0.f;
                                 const float o3 = (3 < kl) ? lw[v].w * ((x1[v].w - mu) * rs) + lb[v].w : 0.f;
-                                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(f.y) + (long long)rm[u].orow * p.N + c) =
-                                    make_uint2(pack_bf2(o0, o1), pack_bf2(o2, o3));
+                                *reinterpret_cast<uint2*>(reinterpret_cast<TI*>(f.y) + (long long)rm[u].orow * p.N + c) =
+                                    make_uint2(Half16<TI>::pk(o0, o1), Half16<TI>::pk(o2, o3));
                             }
                         }
                     }
@@ -411,12 +412,15 @@ __global__ __launch_bounds__(NTHR, NJ > 5 ? 2 : 3) void ntln_kernel(   // (32 x 
 template <int MI, int NJ> int launch(const vr_gemm_args& a, const vr_ln_epilogue& f, hipStream_t stream) {
     const unsigned tiles = (unsigned)vr_gemm_shared::group_tiles(a.M, 16 * MI, a.m_groups);
     const bool ktail = (a.K % BK) != 0;
-    if (f.mode == 0) {
-        if (ktail) hipLaunchKernelGGL((ntln_kernel<MI, NJ, 0, true>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
-        else hipLaunchKernelGGL((ntln_kernel<MI, NJ, 0, false>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
+    if (a.in_dtype == VR_F16) {                     // (forward only: vr_gemm_ln refused mode 1)
+        if (ktail) hipLaunchKernelGGL((ntln_kernel<f16_t, MI, NJ, 0, true>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
+        else hipLaunchKernelGGL((ntln_kernel<f16_t, MI, NJ, 0, false>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
+    } else if (f.mode == 0) {
+        if (ktail) hipLaunchKernelGGL((ntln_kernel<bf16_t, MI, NJ, 0, true>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
+        else hipLaunchKernelGGL((ntln_kernel<bf16_t, MI, NJ, 0, false>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
     } else {
-        if (ktail) hipLaunchKernelGGL((ntln_kernel<MI, NJ, 1, true>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
-        else hipLaunchKernelGGL((ntln_kernel<MI, NJ, 1, false>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
+        if (ktail) hipLaunchKernelGGL((ntln_kernel<bf16_t, MI, NJ, 1, true>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
+        else hipLaunchKernelGGL((ntln_kernel<bf16_t, MI, NJ, 1, false>), dim3(tiles), dim3(NTHR), 0, stream, a, f);
     }
     VR_CHECK_LAUNCH();
     return VR_OK;
@@ -430,7 +434,7 @@ extern "C" int vr_gemm_ln(const vr_gemm_args* g, const vr_ln_epilogue* ln, vr_st
     using namespace vr_gemm_ntln;
     if (!g || !ln || !g->A || !g->B || !g->C || !ln->w || g->M <= 0 || g->N <= 0 || g->K <= 0) return VR_EINVAL;
     const vr_gemm_args& a = *g;
-    if (a.in_dtype != VR_BF16 || a.out_dtype != VR_F32 || a.a_trans || a.b_trans || a.atomic || a.split_k > 1 || a.bias_grad ||
+    if ((a.in_dtype != VR_BF16 && a.in_dtype != VR_F16) || a.out_dtype != VR_F32 || a.a_trans || a.b_trans || a.atomic || a.split_k > 1 || a.bias_grad ||
         a.act || a.dact_u || a.pos || a.C2 || a.n_period > 0 || a.c_map.rpi != 0)
         return VR_EUNSUPPORTED;
     if (!vr_gemm_ln_supported(a.N) || a.ldc % 8 || a.lda % 8 || a.ldb % 8 || a.ldc < a.N) return VR_EUNSUPPORTED;
@@ -439,6 +443,7 @@ extern "C" int vr_gemm_ln(const vr_gemm_args* g, const vr_ln_epilogue* ln, vr_st
     if (ln->mode == 0) {
         if (!ln->b || !ln->y || !ln->mean || !ln->rstd) return VR_EINVAL;
     } else if (ln->mode == 1) {
+        if (a.in_dtype == VR_F16) return VR_EUNSUPPORTED;           // the fp16 mode is forward-only
         if (!ln->x || !ln->mean || !ln->rstd || !ln->dw || !ln->db || a.bias || a.scale || a.keep_n) return VR_EINVAL;
     } else {
         return VR_EINVAL;

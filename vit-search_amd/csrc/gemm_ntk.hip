@@ -30,6 +30,7 @@
 // positional embedding), operands below 4 GB.  Everything else stays with gemm_nt.hip / gemm.hip (vr_gemm_ntk_launch returns false).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "gemm_nt_parts.h"
 #include "lds_dma.h"
@@ -155,7 +156,8 @@ __device__ __forceinline__ void lnf_rows(const vr_gemm_args& p, const vr_ln_epil
 }
 constexpr int LNF_TICKET_OFF = 2048;               // ints: the row blocks' tickets live in the upper half of the ticket area of ws
 
-template <typename TO, int EPI, int MI, int NJ, int NBUF, int FEAT, bool BKM, bool DEEP_EPI = false, bool SPLIT = false, bool LNF = false>
+// TI: the 16-bit operand type (bf16_t, or f16_t for the forward forms of the fp16 mode) -- it selects the MFMA and nothing else
+template <typename TI, typename TO, int EPI, int MI, int NJ, int NBUF, int FEAT, bool BKM, bool DEEP_EPI = false, bool SPLIT = false, bool LNF = false>
 __global__ __launch_bounds__(KTHR, MI == 4 ? 4 : 5) void ntk_kernel(const vr_gemm_args p, const int ksplit, const vr_ln_epilogue ln) {
     constexpr int BM = 32 * MI, WROWS = 16 * MI;
     constexpr int BN = 32 * NJ, WCOLS = 16 * NJ;
@@ -358,7 +360,7 @@ __global__ __launch_bounds__(KTHR, MI == 4 ? 4 : 5) void ntk_kernel(const vr_gem
             for (int i = 0; i < MI; ++i)
 #pragma unroll
                 for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
+                    acc[i][j] = Half16<TI>::mfma16(b[j], a[i], acc[i][j]);
         }
     };
 
@@ -493,16 +495,17 @@ __global__ __launch_bounds__(KTHR, MI == 4 ? 4 : 5) void ntk_kernel(const vr_gem
     }
 }
 
-template <typename TO, int EPI, int MI, int NJ, int NBUF, int FEAT, bool BKM> void klaunch(const vr_gemm_args& a, hipStream_t stream, int shares,
+template <typename TI, typename TO, int EPI, int MI, int NJ, int NBUF, int FEAT, bool BKM> void klaunch(const vr_gemm_args& a, hipStream_t stream, int shares,
                                                                                              const vr_ln_epilogue* ln) {
     const vr_ln_epilogue ln0 = ln ? *ln : vr_ln_epilogue{};
     const long long total = (long long)group_tiles(a.M, 32 * MI, a.m_groups) * ((a.N + 32 * NJ - 1) / (32 * NJ));
     constexpr bool SIDE = (EPI == EPI_STORE && FEAT >= 2) || EPI == EPI_DMUL;
     // the forms of the block Linears have a split kernel (FEAT 2: a block without DropPath -- the first one -- is never a long-K one)
-    constexpr bool CAN_SPLIT = NBUF <= 3 && ((EPI == EPI_STORE && (FEAT == 0 || FEAT == 1 || FEAT == 3)) || EPI == EPI_GELU || EPI == EPI_DMUL);
-    if constexpr (sizeof(TO) == 4 && EPI == EPI_STORE && FEAT >= 2 && !BKM && NBUF <= 3 && MI == 2 && NJ == 4) {     // (64 x 128 tiles)
+    constexpr bool BF = std::is_same_v<TI, bf16_t>;              // (the K-split and LayerNorm-folding forms are bf16-only)
+    constexpr bool CAN_SPLIT = BF && NBUF <= 3 && ((EPI == EPI_STORE && (FEAT == 0 || FEAT == 1 || FEAT == 3)) || EPI == EPI_GELU || EPI == EPI_DMUL);
+    if constexpr (BF && sizeof(TO) == 4 && EPI == EPI_STORE && FEAT >= 2 && !BKM && NBUF <= 3 && MI == 2 && NJ == 4) {     // (64 x 128 tiles)
         if (ln) {
-            hipLaunchKernelGGL((ntk_kernel<TO, EPI, MI, NJ, NBUF, FEAT, BKM, true, false, true>), dim3((unsigned)total), dim3(KTHR), 0, stream, a, 1,
+            hipLaunchKernelGGL((ntk_kernel<TI, TO, EPI, MI, NJ, NBUF, FEAT, BKM, true, false, true>), dim3((unsigned)total), dim3(KTHR), 0, stream, a, 1,
                                ln0);
             return;
         }
@@ -510,36 +513,56 @@ template <typename TO, int EPI, int MI, int NJ, int NBUF, int FEAT, bool BKM> vo
     if constexpr (CAN_SPLIT) {
         if (shares > 1) {
             const unsigned grid = (unsigned)(8 * ((total + 7) / 8) * shares);
-            hipLaunchKernelGGL((ntk_kernel<TO, EPI, MI, NJ, NBUF, FEAT, BKM, MI == 2 && SIDE, true>), dim3(grid), dim3(KTHR), 0, stream, a, shares, ln0);
+            hipLaunchKernelGGL((ntk_kernel<TI, TO, EPI, MI, NJ, NBUF, FEAT, BKM, MI == 2 && SIDE, true>), dim3(grid), dim3(KTHR), 0, stream, a, shares, ln0);
             return;
         }
     }
-    hipLaunchKernelGGL((ntk_kernel<TO, EPI, MI, NJ, NBUF, FEAT, BKM, MI == 2 && SIDE>), dim3((unsigned)total), dim3(KTHR), 0, stream, a, 1, ln0);
+    hipLaunchKernelGGL((ntk_kernel<TI, TO, EPI, MI, NJ, NBUF, FEAT, BKM, MI == 2 && SIDE>), dim3((unsigned)total), dim3(KTHR), 0, stream, a, 1, ln0);
 }
 
-template <typename TO, int EPI, int FEAT, bool BKM> void ktile(const vr_gemm_args& a, hipStream_t stream, int tile, int nbuf, int shares,
+template <typename TI, typename TO, int EPI, int FEAT, bool BKM> void ktile(const vr_gemm_args& a, hipStream_t stream, int tile, int nbuf, int shares,
                                                                 const vr_ln_epilogue* ln = nullptr) {
     if (tile == 1) {
-        if (nbuf == 1) klaunch<TO, EPI, 4, 4, 1, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 2) klaunch<TO, EPI, 4, 4, 2, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 3) klaunch<TO, EPI, 4, 4, 3, FEAT, BKM>(a, stream, shares, ln);
-        else klaunch<TO, EPI, 4, 4, 4, FEAT, BKM>(a, stream, 1, ln);
+        if (nbuf == 1) klaunch<TI, TO, EPI, 4, 4, 1, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 2) klaunch<TI, TO, EPI, 4, 4, 2, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 3) klaunch<TI, TO, EPI, 4, 4, 3, FEAT, BKM>(a, stream, shares, ln);
+        else klaunch<TI, TO, EPI, 4, 4, 4, FEAT, BKM>(a, stream, 1, ln);
     } else if (tile == 2) {
-        if (nbuf == 1) klaunch<TO, EPI, 2, 4, 1, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 2) klaunch<TO, EPI, 2, 4, 2, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 3) klaunch<TO, EPI, 2, 4, 3, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 4) klaunch<TO, EPI, 2, 4, 4, FEAT, BKM>(a, stream, 1, ln);
-        else if (nbuf == 5) klaunch<TO, EPI, 2, 4, 5, FEAT, BKM>(a, stream, 1, ln);
-        else klaunch<TO, EPI, 2, 4, 6, FEAT, BKM>(a, stream, 1, ln);
+        if (nbuf == 1) klaunch<TI, TO, EPI, 2, 4, 1, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 2) klaunch<TI, TO, EPI, 2, 4, 2, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 3) klaunch<TI, TO, EPI, 2, 4, 3, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 4) klaunch<TI, TO, EPI, 2, 4, 4, FEAT, BKM>(a, stream, 1, ln);
+        else if (nbuf == 5) klaunch<TI, TO, EPI, 2, 4, 5, FEAT, BKM>(a, stream, 1, ln);
+        else klaunch<TI, TO, EPI, 2, 4, 6, FEAT, BKM>(a, stream, 1, ln);
     } else {
-        if (nbuf == 1) klaunch<TO, EPI, 2, 2, 1, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 2) klaunch<TO, EPI, 2, 2, 2, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 3) klaunch<TO, EPI, 2, 2, 3, FEAT, BKM>(a, stream, shares, ln);
-        else if (nbuf == 4) klaunch<TO, EPI, 2, 2, 4, FEAT, BKM>(a, stream, 1, ln);
-        else klaunch<TO, EPI, 2, 2, 6, FEAT, BKM>(a, stream, 1, ln);
+        if (nbuf == 1) klaunch<TI, TO, EPI, 2, 2, 1, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 2) klaunch<TI, TO, EPI, 2, 2, 2, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 3) klaunch<TI, TO, EPI, 2, 2, 3, FEAT, BKM>(a, stream, shares, ln);
+        else if (nbuf == 4) klaunch<TI, TO, EPI, 2, 2, 4, FEAT, BKM>(a, stream, 1, ln);
+        else klaunch<TI, TO, EPI, 2, 2, 6, FEAT, BKM>(a, stream, 1, ln);
     }
 }
 
+}  // namespace vr_gemm_nt
+
+namespace vr_gemm_nt {
+// the EPI_STORE forms of the forward (fp32 or 16-bit result)
+template <typename TI> bool ntk_store(const vr_gemm_args& a, hipStream_t stream, int tile, int nbuf, int shares, const vr_ln_epilogue* ln,
+                                      bool of32, int feat) {
+    if (of32) {
+        if (ln) nbuf = std::min(nbuf, 3);
+        if (feat == 3) ktile<TI, float, EPI_STORE, 3, false>(a, stream, tile, nbuf, shares, ln);
+        else if (feat == 2) ktile<TI, float, EPI_STORE, 2, false>(a, stream, tile, nbuf, shares, ln);
+        else if (feat == 1 && !ln) ktile<TI, float, EPI_STORE, 1, false>(a, stream, tile, nbuf, shares);
+        else return false;
+        return true;
+    }
+    if (ln) return false;
+    if (feat == 1) ktile<TI, TI, EPI_STORE, 1, false>(a, stream, tile, nbuf, shares);
+    else if (feat == 0) ktile<TI, TI, EPI_STORE, 0, false>(a, stream, tile, nbuf, shares);
+    else return false;
+    return true;
+}
 }  // namespace vr_gemm_nt
 
 bool vr_gemm_panel_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu);      // gemm_panel.hip: panel-resident stage-1 kernels
@@ -558,7 +581,9 @@ bool vr_gemm_ntk_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu, con
     if (a.sched & (8 | 16 | 32 | 0x100)) return false;      // forms of gemm_nt.hip forced by the caller (tests, measurement aids)
     // an operand with unwritten masked tiles (0x80000) is readable only by the group-pure row tiling: refused where it cannot be had
     if ((a.sched & 0x80000) && a.keep_k && a.m_groups > 1 && !group_pure(a.M, a.m_groups)) return false;
-    if (a.in_dtype != VR_BF16 || a.a_trans || a.atomic || a.split_k > 1 || a.bias_grad || a.pos) return false;
+    const bool f16 = a.in_dtype == VR_F16;
+    if ((a.in_dtype != VR_BF16 && !f16) || a.a_trans || a.atomic || a.split_k > 1 || a.bias_grad || a.pos) return false;
+    if (f16 && (ln || a.b_trans || a.dact_u)) return false;          // fp16: the forward forms only
     if (a.K % BK || a.K > 64 * BK || a.K < BK) return false;
     const bool fast = a.N % 8 == 0 && a.ldc % 8 == 0 && (!a.dact_u || a.ldu % 8 == 0) && (a.n_period <= 0 || a.n_period % 8 == 0);
     if (!fast || a.lda % 8 || a.ldb % 8 || ((uintptr_t)a.A & 15) || ((uintptr_t)a.B & 15)) return false;
@@ -602,7 +627,7 @@ bool vr_gemm_ntk_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu, con
     const int ntiles = a.K / BK;
     int shares = 1;
     constexpr int rule_tile = 0, rule_ring = 0;
-    if (split_form && a.k_shares > 1 && !ln) shares = std::min(std::min(a.k_shares, 4), std::max(1, ntiles / 2));
+    if (split_form && a.k_shares > 1 && !ln && !f16) shares = std::min(std::min(a.k_shares, 4), std::max(1, ntiles / 2));
     const int tile = s_tile ? s_tile : (rule_tile ? rule_tile : auto_tile);
     const long long wgs = (long long)group_tiles(a.M, tile == 1 ? 128 : 64, a.m_groups) * ((a.N + (tile == 3 ? 63 : 127)) / (tile == 3 ? 64 : 128));
     const int stage_kb = tile == 1 ? 32 : (tile == 2 ? 24 : 16);
@@ -632,29 +657,19 @@ bool vr_gemm_ntk_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu, con
         if (of32 || feat != 0 || gelu || a.b_map.rpi != 0 || a.ldb < (a.N + 7) / 8 * 8) return false;
         if (a.dact_u) {
             if (a.act != 2) return false;
-            ktile<bf16_t, EPI_DMUL, 0, true>(a, stream, tile, nbuf, shares);
+            ktile<bf16_t, bf16_t, EPI_DMUL, 0, true>(a, stream, tile, nbuf, shares);
         } else {
-            ktile<bf16_t, EPI_STORE, 0, true>(a, stream, tile, nbuf, shares);
+            ktile<bf16_t, bf16_t, EPI_STORE, 0, true>(a, stream, tile, nbuf, shares);
         }
         return true;
     }
     if (a.dact_u) return false;
     if (gelu) {
         if (of32 || feat != 1 || a.act == 3) return false;
-        ktile<bf16_t, EPI_GELU, 1, false>(a, stream, tile, nbuf, shares);
+        if (f16) ktile<f16_t, f16_t, EPI_GELU, 1, false>(a, stream, tile, nbuf, shares);
+        else ktile<bf16_t, bf16_t, EPI_GELU, 1, false>(a, stream, tile, nbuf, shares);
         return true;
     }
-    if (of32) {
-        if (ln) nbuf = std::min(nbuf, 3);
-        if (feat == 3) ktile<float, EPI_STORE, 3, false>(a, stream, tile, nbuf, shares, ln);
-        else if (feat == 2) ktile<float, EPI_STORE, 2, false>(a, stream, tile, nbuf, shares, ln);
-        else if (feat == 1 && !ln) ktile<float, EPI_STORE, 1, false>(a, stream, tile, nbuf, shares);
-        else return false;
-        return true;
-    }
-    if (ln) return false;
-    if (feat == 1) ktile<bf16_t, EPI_STORE, 1, false>(a, stream, tile, nbuf, shares);
-    else if (feat == 0) ktile<bf16_t, EPI_STORE, 0, false>(a, stream, tile, nbuf, shares);
-    else return false;
-    return true;
+    return f16 ? ntk_store<f16_t>(a, stream, tile, nbuf, shares, ln, of32, feat)
+               : ntk_store<bf16_t>(a, stream, tile, nbuf, shares, ln, of32, feat);
 }

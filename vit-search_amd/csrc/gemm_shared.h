@@ -117,13 +117,13 @@ template <typename TI, int CW> __device__ __forceinline__ void loadw(const void*
             const uint32_t w[4] = {u.x, u.y, u.z, u.w};
 #pragma unroll
             for (int h = 0; h < 4; ++h) {
-                v[2 * h] = __uint_as_float(w[h] << 16);
-                v[2 * h + 1] = __uint_as_float(w[h] & 0xffff0000u);
+                v[2 * h] = Half16<TI>::lo(w[h]);
+                v[2 * h + 1] = Half16<TI>::hi(w[h]);
             }
         } else {
             const uint2 u = *reinterpret_cast<const uint2*>(p);
-            v[0] = __uint_as_float(u.x << 16); v[1] = __uint_as_float(u.x & 0xffff0000u);
-            v[2] = __uint_as_float(u.y << 16); v[3] = __uint_as_float(u.y & 0xffff0000u);
+            v[0] = Half16<TI>::lo(u.x); v[1] = Half16<TI>::hi(u.x);
+            v[2] = Half16<TI>::lo(u.y); v[3] = Half16<TI>::hi(u.y);
         }
     } else {
 #pragma unroll
@@ -147,10 +147,10 @@ template <typename TO, int CW, bool WT = false> __device__ __forceinline__ void 
             for (int h = 0; h < CW / 4; ++h)
                 *reinterpret_cast<float4*>(p + 4 * h) = make_float4(v[4 * h], v[4 * h + 1], v[4 * h + 2], v[4 * h + 3]);
         } else if constexpr (CW == 8) {
-            *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]),
-                                                      pack_bf2(v[6], v[7]));
+            *reinterpret_cast<uint4*>(p) = make_uint4(Half16<TO>::pk(v[0], v[1]), Half16<TO>::pk(v[2], v[3]),
+                                                      Half16<TO>::pk(v[4], v[5]), Half16<TO>::pk(v[6], v[7]));
         } else {
-            *reinterpret_cast<uint2*>(p) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+            *reinterpret_cast<uint2*>(p) = make_uint2(Half16<TO>::pk(v[0], v[1]), Half16<TO>::pk(v[2], v[3]));
         }
     } else {
 #pragma unroll

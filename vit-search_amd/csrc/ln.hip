@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                 if constexpr (sizeof(TO) == 4) {
                     *reinterpret_cast<float4*>(yr + c) = make_float4(o0, o1, o2, o3);
                 } else {
-                    *reinterpret_cast<uint2*>(yr + c) = make_uint2(pack_bf2(o0, o1), pack_bf2(o2, o3));
+                    *reinterpret_cast<uint2*>(yr + c) = make_uint2(Half16<TO>::pk(o0, o1), Half16<TO>::pk(o2, o3));
                 }
             }
         }
@@ -271,7 +271,7 @@ extern "C" int vr_ln_fwd(const float* x, const float* w, const float* b, void* y
                          int32_t out_dtype, vr_stream_t stream) {
     if (!x || !w || !b || !y || !mean || !rstd || M <= 0 || C <= 0) return VR_EINVAL;
     if (C % 4 || C > 64 * 4 * MAXV_LIMIT) return VR_EUNSUPPORTED;
-    if (out_dtype != VR_F32 && out_dtype != VR_BF16) return VR_EUNSUPPORTED;
+    if (out_dtype != VR_F32 && out_dtype != VR_BF16 && out_dtype != VR_F16) return VR_EUNSUPPORTED;
     if (rows_per_sample <= 0) rows_per_sample = M;
     constexpr int knob_xcd = 1;                     // XCD-contiguous row ranges (common.h xcd_block), forward and backward
     const int nv = (C + 255) / 256;
@@ -282,6 +282,9 @@ extern "C" int vr_ln_fwd(const float* x, const float* w, const float* b, void* y
     if (out_dtype == VR_F32)                                                                                           \
         hipLaunchKernelGGL((ln_fwd_kernel<float, NV, R>), grid, dim3(256), 0, (hipStream_t)stream, x, w, b, (float*)y, mean, \
                            rstd, keep, M, C, rows_per_sample, eps, knob_xcd);                                                    \
+    else if (out_dtype == VR_F16)                                                                                      \
+        hipLaunchKernelGGL((ln_fwd_kernel<f16_t, NV, R>), grid, dim3(256), 0, (hipStream_t)stream, x, w, b, (f16_t*)y,    \
+                           mean, rstd, keep, M, C, rows_per_sample, eps, knob_xcd);                                                \
     else                                                                                                               \
         hipLaunchKernelGGL((ln_fwd_kernel<bf16_t, NV, R>), grid, dim3(256), 0, (hipStream_t)stream, x, w, b, (bf16_t*)y,  \
                            mean, rstd, keep, M, C, rows_per_sample, eps, knob_xcd);

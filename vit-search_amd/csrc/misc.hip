@@ -5,17 +5,18 @@
 
 namespace {
 
-// ---- fp32 -> bf16 ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long long n) {
+// ---- fp32 -> bf16 / fp16 ------------------------------------------------------------------------------
+template <typename TD>
+__global__ __launch_bounds__(256) void cast_kernel(const float* __restrict__ src, TD* __restrict__ dst, long long n) {
     const long long stride = (long long)gridDim.x * blockDim.x * 8;
     for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < n; i += stride) {
         if (i + 8 <= n) {
             const float4 a = *reinterpret_cast<const float4*>(src + i);
             const float4 b = *reinterpret_cast<const float4*>(src + i + 4);
             *reinterpret_cast<uint4*>(dst + i) =
-                make_uint4(pack_bf2(a.x, a.y), pack_bf2(a.z, a.w), pack_bf2(b.x, b.y), pack_bf2(b.z, b.w));
+                make_uint4(Half16<TD>::pk(a.x, a.y), Half16<TD>::pk(a.z, a.w), Half16<TD>::pk(b.x, b.y), Half16<TD>::pk(b.z, b.w));
         } else {
-            for (long long j = i; j < n; ++j) dst[j] = f2bf(src[j]);
+            for (long long j = i; j < n; ++j) Elem<TD>::st(dst + j, src[j]);
         }
     }
 }
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(256) void scale_mask_cast_kernel(const float* __res
         v.z = (c + 2 < kc) ? v.z * sc : 0.f;
         v.w = (c + 3 < kc) ? v.w * sc : 0.f;
         if constexpr (sizeof(T) == 4) *reinterpret_cast<float4*>(dst + c) = v;
-        else *reinterpret_cast<uint2*>(dst + c) = make_uint2(pack_bf2(v.x, v.y), pack_bf2(v.z, v.w));
+        else *reinterpret_cast<uint2*>(dst + c) = make_uint2(Half16<T>::pk(v.x, v.y), Half16<T>::pk(v.z, v.w));
     }
 }
 
@@ -305,7 +306,8 @@ __global__ __launch_bounds__(256) void im2col_patch_kernel(const float* __restri
     __syncthreads();
     const int K = Cin * P * P;
     T* out = col + ((long long)bo * gh + py) * gw * ldk;
-    if (sizeof(T) == 2 && ldk % 8 == 0 && (reinterpret_cast<uintptr_t>(col) & 15) == 0) {
+    if constexpr (sizeof(T) == 2) {
+      if (ldk % 8 == 0 && (reinterpret_cast<uintptr_t>(col) & 15) == 0) {
         // eight consecutive k per thread, one 16-byte store: (c, i, j) is decoded once per group and stepped with carries -- the
         // element-per-thread form spent ~40 integer instructions (three divisions by run-time values) on every 2-byte store
         const int g8 = ldk / 8;
@@ -319,10 +321,11 @@ __global__ __launch_bounds__(256) void im2col_patch_kernel(const float* __restri
                 f[e] = (k0 + e < K) ? src[r * W + j] : 0.f;
                 if (++j == P) { j = 0; ++r; }
             }
-            *reinterpret_cast<uint4*>(reinterpret_cast<bf16_t*>(out) + (long long)px * ldk + k0) =
-                make_uint4(pack_bf2(f[0], f[1]), pack_bf2(f[2], f[3]), pack_bf2(f[4], f[5]), pack_bf2(f[6], f[7]));
+            *reinterpret_cast<uint4*>(out + (long long)px * ldk + k0) =
+                make_uint4(Half16<T>::pk(f[0], f[1]), Half16<T>::pk(f[2], f[3]), Half16<T>::pk(f[4], f[5]), Half16<T>::pk(f[6], f[7]));
         }
         return;
+      }
     }
     for (int idx = threadIdx.x; idx < gw * ldk; idx += blockDim.x) {
         const int px = idx / ldk, k = idx % ldk;
@@ -497,16 +500,19 @@ __global__ __launch_bounds__(256) void sr_resid_bwd_kernel(const float* __restri
 
 extern "C" int vr_version(void) { return 1000; }
 
-extern "C" int vr_cast_f32_bf16(const float* src, void* dst, int64_t n, vr_stream_t stream) {
+template <typename TD> static int cast_f32(const float* src, void* dst, int64_t n, vr_stream_t stream) {
     if (!src || !dst || n <= 0) return VR_EINVAL;
     if (((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return VR_EALIGN;
     long long blocks = (n / 8 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(cast_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (bf16_t*)dst, (long long)n);
+    hipLaunchKernelGGL(cast_kernel<TD>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src, (TD*)dst, (long long)n);
     VR_CHECK_LAUNCH();
     return VR_OK;
 }
+
+extern "C" int vr_cast_f32_bf16(const float* src, void* dst, int64_t n, vr_stream_t stream) { return cast_f32<bf16_t>(src, dst, n, stream); }
+extern "C" int vr_cast_f32_f16(const float* src, void* dst, int64_t n, vr_stream_t stream) { return cast_f32<f16_t>(src, dst, n, stream); }
 
 extern "C" int vr_cast_transpose_batch(const float* src, void* dst, const vr_tr_desc* descs, int32_t n, int32_t max_tiles,
                                        vr_stream_t stream) {
@@ -576,6 +582,8 @@ extern "C" int vr_scale_mask_cast(const float* in, void* out, const float* scale
         hipLaunchKernelGGL((scale_mask_cast_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, in, (float*)out, scale, keep, M, C, rows_per_sample);
     else if (out_dtype == VR_BF16)
         hipLaunchKernelGGL((scale_mask_cast_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, in, (bf16_t*)out, scale, keep, M, C, rows_per_sample);
+    else if (out_dtype == VR_F16)
+        hipLaunchKernelGGL((scale_mask_cast_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream, in, (f16_t*)out, scale, keep, M, C, rows_per_sample);
     else
         return VR_EUNSUPPORTED;
     VR_CHECK_LAUNCH();
@@ -589,6 +597,8 @@ extern "C" int vr_token_mean(const void* y, void* out, int32_t B, int32_t N, int
         hipLaunchKernelGGL((token_mean_kernel<float>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const float*)y, (float*)out, N, C, first);
     else if (dtype == VR_BF16)
         hipLaunchKernelGGL((token_mean_kernel<bf16_t>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, (bf16_t*)out, N, C, first);
+    else if (dtype == VR_F16)
+        hipLaunchKernelGGL((token_mean_kernel<f16_t>), dim3(B), dim3(256), 0, (hipStream_t)stream, (const f16_t*)y, (f16_t*)out, N, C, first);
     else
         return VR_EUNSUPPORTED;
     VR_CHECK_LAUNCH();
@@ -634,6 +644,8 @@ extern "C" int vr_im2col_patch_map(const float* img, void* col, const int64_t* s
         hipLaunchKernelGGL((im2col_patch_kernel<float>), grid, dim3(256), lds, (hipStream_t)stream, img, (float*)col, B, Cin, H, W, P, ldk, smap);
     else if (dtype == VR_BF16)
         hipLaunchKernelGGL((im2col_patch_kernel<bf16_t>), grid, dim3(256), lds, (hipStream_t)stream, img, (bf16_t*)col, B, Cin, H, W, P, ldk, smap);
+    else if (dtype == VR_F16)
+        hipLaunchKernelGGL((im2col_patch_kernel<f16_t>), grid, dim3(256), lds, (hipStream_t)stream, img, (f16_t*)col, B, Cin, H, W, P, ldk, smap);
     else
         return VR_EUNSUPPORTED;
     VR_CHECK_LAUNCH();
@@ -660,7 +672,8 @@ extern "C" int vr_sr_im2col(const void* y, void* col, int32_t B, int32_t g, int3
     if (!y || !col || B <= 0 || g <= 0 || (g & 1) || num_tokens < 1) return VR_EINVAL;
     const int NT = num_tokens;
     dim3 grid(B * (g / 2) * (g / 2), 9);
-    if (dtype == VR_BF16 && C % 8 == 0 && !((uintptr_t)y & 15) && !((uintptr_t)col & 15)) {
+    if ((dtype == VR_BF16 || dtype == VR_F16) && C % 8 == 0 && !((uintptr_t)y & 15) && !((uintptr_t)col & 15)) {
+        // (raw 16-bit lanes: the same copy for bf16 and fp16)
         const long long total = (long long)B * (g / 2) * (g / 2) * 9 * (C / 8);
         const long long blocks = (total + 255) / 256;
         hipLaunchKernelGGL(sr_im2col_v8_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, (hipStream_t)stream,
@@ -669,6 +682,8 @@ extern "C" int vr_sr_im2col(const void* y, void* col, int32_t B, int32_t g, int3
         hipLaunchKernelGGL((sr_im2col_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)y, (float*)col, B, g, C, NT);
     else if (dtype == VR_BF16)
         hipLaunchKernelGGL((sr_im2col_kernel<bf16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)y, (bf16_t*)col, B, g, C, NT);
+    else if (dtype == VR_F16)
+        hipLaunchKernelGGL((sr_im2col_kernel<f16_t>), grid, dim3(256), 0, (hipStream_t)stream, (const f16_t*)y, (f16_t*)col, B, g, C, NT);
     else
         return VR_EUNSUPPORTED;
     VR_CHECK_LAUNCH();
@@ -757,7 +772,7 @@ extern "C" int vr_zero_ranges(float* base, const vr_range_list* ranges, vr_strea
     return VR_OK;
 }
 
-// ---- vr_relayout: dst[a * dst_ld + c * B + b] = src[a * src_ld + b * C + c]  (fp32 / bf16 in, fp32 / bf16 out) ----
+// ---- vr_relayout: dst[a * dst_ld + c * B + b] = src[a * src_ld + b * C + c]  (fp32 / bf16 / fp16 in and out; bf16 and fp16 are not mixed) ----
 // The small re-layouts around the convolution-shaped weights: [out][in][taps] -> [out][(taps, in)] for the GEMM form of the 3x3 /
 // 7x7 convolutions (nets/patch_conv.py:56-58, vit_sr_supernet.py:140) and back for their gradients; with B = 1 a row copy into
 // 16-byte-aligned rows (the timm PatchEmbed weight, k = 588 -> ld = 592).  Pad columns of dst are not touched.
@@ -790,6 +805,12 @@ extern "C" int vr_relayout(const void* src, void* dst, int32_t A, int32_t B, int
         hipLaunchKernelGGL((relayout_kernel<bf16_t, bf16_t>), dim3(grid), dim3(256), 0, st, (const bf16_t*)src, (bf16_t*)dst, A, B, C, src_ld, dst_ld);
     else if (src_dtype == VR_BF16 && dst_dtype == VR_F32)
         hipLaunchKernelGGL((relayout_kernel<bf16_t, float>), dim3(grid), dim3(256), 0, st, (const bf16_t*)src, (float*)dst, A, B, C, src_ld, dst_ld);
+    else if (src_dtype == VR_F32 && dst_dtype == VR_F16)
+        hipLaunchKernelGGL((relayout_kernel<float, f16_t>), dim3(grid), dim3(256), 0, st, (const float*)src, (f16_t*)dst, A, B, C, src_ld, dst_ld);
+    else if (src_dtype == VR_F16 && dst_dtype == VR_F16)
+        hipLaunchKernelGGL((relayout_kernel<f16_t, f16_t>), dim3(grid), dim3(256), 0, st, (const f16_t*)src, (f16_t*)dst, A, B, C, src_ld, dst_ld);
+    else if (src_dtype == VR_F16 && dst_dtype == VR_F32)
+        hipLaunchKernelGGL((relayout_kernel<f16_t, float>), dim3(grid), dim3(256), 0, st, (const f16_t*)src, (float*)dst, A, B, C, src_ld, dst_ld);
     else
         return VR_EUNSUPPORTED;
     VR_CHECK_LAUNCH();

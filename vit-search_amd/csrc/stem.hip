@@ -61,7 +61,8 @@ __global__ __launch_bounds__(256) void im2col3x3_nchw_kernel(const float* __rest
 // The same for the shape the patch embedding uses (3 channels, bf16, ld = 32): one thread per output pixel gathers its 27 values and
 // writes the whole 64-byte row with four 16-byte stores -- the element-per-thread form above ran at 0.6 TB/s (three integer
 // divisions per 2-byte store).  Consecutive threads = consecutive output columns: their image reads share cache lines.
-__global__ __launch_bounds__(256) void im2col3x3_nchw3_row_kernel(const float* __restrict__ img, bf16_t* __restrict__ col, int B, int H,
+template <typename T>
+__global__ __launch_bounds__(256) void im2col3x3_nchw3_row_kernel(const float* __restrict__ img, T* __restrict__ col, int B, int H,
                                                                   int W, int stride, long long rows) {
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
     for (long long row = (long long)blockIdx.x * 256 + threadIdx.x; row < rows; row += (long long)gridDim.x * 256) {
@@ -81,8 +82,8 @@ __global__ __launch_bounds__(256) void im2col3x3_nchw3_row_kernel(const float* _
         uint4* dst = reinterpret_cast<uint4*>(col + row * 32);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            dst[q] = make_uint4(pack_bf2(v[8 * q], v[8 * q + 1]), pack_bf2(v[8 * q + 2], v[8 * q + 3]), pack_bf2(v[8 * q + 4], v[8 * q + 5]),
-                                pack_bf2(v[8 * q + 6], v[8 * q + 7]));
+            dst[q] = make_uint4(Half16<T>::pk(v[8 * q], v[8 * q + 1]), Half16<T>::pk(v[8 * q + 2], v[8 * q + 3]),
+                                Half16<T>::pk(v[8 * q + 4], v[8 * q + 5]), Half16<T>::pk(v[8 * q + 6], v[8 * q + 7]));
     }
 }
 
@@ -332,22 +333,29 @@ inline unsigned grid_for(long long total) {
 extern "C" int vr_im2col3x3(const void* src, void* col, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
                             int32_t src_nchw_f32, int32_t ld, int32_t dtype, vr_stream_t stream) {
     if (!src || !col || B <= 0 || H <= 0 || W <= 0 || C <= 0) return VR_EINVAL;
-    if (dtype != VR_F32 && dtype != VR_BF16) return VR_EUNSUPPORTED;
+    if (dtype != VR_F32 && dtype != VR_BF16 && dtype != VR_F16) return VR_EUNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (src_nchw_f32) {
         if (ld < 9 * C) return VR_EINVAL;
         const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
         const long long total = (long long)B * Ho * Wo * ld;
-        if (dtype == VR_BF16 && C == 3 && ld == 32 && ((uintptr_t)col & 15) == 0) {
+        if (dtype != VR_F32 && C == 3 && ld == 32 && ((uintptr_t)col & 15) == 0) {
             const long long rows = (long long)B * Ho * Wo;
-            hipLaunchKernelGGL(im2col3x3_nchw3_row_kernel, dim3(grid_for(rows)), dim3(256), 0, st, (const float*)src, (bf16_t*)col, B, H, W,
-                               stride, rows);
+            if (dtype == VR_F16)
+                hipLaunchKernelGGL((im2col3x3_nchw3_row_kernel<f16_t>), dim3(grid_for(rows)), dim3(256), 0, st, (const float*)src, (f16_t*)col, B, H,
+                                   W, stride, rows);
+            else
+                hipLaunchKernelGGL((im2col3x3_nchw3_row_kernel<bf16_t>), dim3(grid_for(rows)), dim3(256), 0, st, (const float*)src, (bf16_t*)col, B,
+                                   H, W, stride, rows);
         } else if (dtype == VR_F32)
             hipLaunchKernelGGL((im2col3x3_nchw_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)src, (float*)col, B, C, H, W, stride, ld, total);
+        else if (dtype == VR_F16)
+            hipLaunchKernelGGL((im2col3x3_nchw_kernel<f16_t>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)src, (f16_t*)col, B, C, H, W, stride, ld, total);
         else
             hipLaunchKernelGGL((im2col3x3_nchw_kernel<bf16_t>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)src, (bf16_t*)col, B, C, H, W, stride, ld, total);
     } else {
         if (stride != 1 || C % 8 || ld != 9 * C) return VR_EUNSUPPORTED;
+        if (dtype == VR_F16) return VR_EUNSUPPORTED;                   // (fp16: the evaluation stem gathers from the image only)
         const long long total = (long long)B * H * W * 9 * (C / 8);
         if (dtype == VR_F32)
             hipLaunchKernelGGL((im2col3x3_nhwc_kernel<float>), dim3(grid_for(total)), dim3(256), 0, st, (const float*)src, (float*)col, B, H, W, C, total);
@@ -504,6 +512,8 @@ extern "C" int vr_patch_unfold(void* a, void* col, int32_t B, int32_t gh, int32_
     if (dtype == VR_F32) {
         if (fold) hipLaunchKernelGGL((patch_unfold_kernel<float, true>), dim3(grid_for(total)), dim3(256), 0, st, (float*)a, (float*)col, B, gh, gw, P, C, total);
         else hipLaunchKernelGGL((patch_unfold_kernel<float, false>), dim3(grid_for(total)), dim3(256), 0, st, (float*)a, (float*)col, B, gh, gw, P, C, total);
+    } else if (dtype == VR_F16 && !fold) {         // (fp16: the evaluation stem's unfold; raw 16-bit lanes, the bf16 copy)
+        hipLaunchKernelGGL((patch_unfold_kernel<bf16_t, false>), dim3(grid_for(total)), dim3(256), 0, st, (bf16_t*)a, (bf16_t*)col, B, gh, gw, P, C, total);
     } else if (dtype == VR_BF16) {
         if (fold) hipLaunchKernelGGL((patch_unfold_kernel<bf16_t, true>), dim3(grid_for(total)), dim3(256), 0, st, (bf16_t*)a, (bf16_t*)col, B, gh, gw, P, C, total);
         else hipLaunchKernelGGL((patch_unfold_kernel<bf16_t, false>), dim3(grid_for(total)), dim3(256), 0, st, (bf16_t*)a, (bf16_t*)col, B, gh, gw, P, C, total);

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # VITRES_LIB: another build of the same ABI (A/B timing of kernel changes on one box: tools/ab.sh)
 LIB_PATH = os.environ.get("VITRES_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvitres_hip.so")
 
-VR_F32, VR_BF16 = 0, 1
+VR_F32, VR_BF16, VR_F16 = 0, 1, 2
 
 
 class RowMap(ctypes.Structure):
@@ -62,6 +62,7 @@ SYMBOLS = {
     "vr_gemm_ln_fold": [ctypes.POINTER(GemmArgs), ctypes.POINTER(LnEpilogue), c_void_p],
     "vr_gemm_ws_bytes": [],
     "vr_cast_f32_bf16": [c_void_p, c_void_p, c_int64, c_void_p],
+    "vr_cast_f32_f16": [c_void_p, c_void_p, c_int64, c_void_p],
     "vr_adamw_flat": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_void_p],
     "vr_adamw_flat_dev": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_void_p],
     "vr_adamw_flat_dev_capped": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p],

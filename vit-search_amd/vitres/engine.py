@@ -292,6 +292,8 @@ class GraphedTrainStep:
         of the backward -- most of the time -- is still running.
         opt_overlap / opt_overlap_blocks (with optimizer): number of arena ranges updated early, beside the rest of the backward,
         and the workgroup cap of those updates (see below)."""
+        if hasattr(model, "_check_fp16_eval"):
+            model._check_fp16_eval(True)          # (fp16 is an evaluation mode: nothing is captured or launched)
         self.model, self.criterion, self.pot = model, criterion, patch_output_type
         self.graph_b, self.split, self.more_graphs, self.ranges = None, None, [], []
         self._inflight = []
@@ -437,6 +439,8 @@ class GraphedTrainStep:
         return self.criterion(cls_pred, self.t) + self.criterion(patch_pred, self.pt if self.pot == 'seq' else self.t)
 
     def __call__(self, samples, targets, patch_targets=None, epoch=0, train_iter=0, arch_sample=None):
+        if hasattr(self.model, "_check_fp16_eval"):
+            self.model._check_fp16_eval(True)     # (the model was switched to fp16 after the capture: no replay)
         rng = None
         if arch_sample is not None:                                # engine.py:119-131
             rng = torch.random.get_rng_state()

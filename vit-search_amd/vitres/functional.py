@@ -340,7 +340,7 @@ def mlp_branch_fwd(x, p, cfg, embed_keep, mlp_keep, out_keep, scale, save, pre=N
         # data gradient becomes a plain multiply (its erf / exp per element made that kernel VALU-bound); fp32 parity mode keeps u
         u = torch.empty((B, N, F), dtype=dt, device=x.device)
         K.gemm(y, p["fc1"].w_c, u, out2=h, M=M, N=F, K=C, lda=C, ldb=p["fc1"].ld, ldc=F, bias=p["fc1"].b,
-               act=(2 if dt == torch.bfloat16 else 1), keep_n=mlp_keep, rows_in=N, keep_k=embed_keep)
+               act=(2 if K.is_fast16(dt) else 1), keep_n=mlp_keep, rows_in=N, keep_k=embed_keep)
     else:                                       # forward-only: the pre-activation is not kept, fc1 writes gelu(u) alone
         u = None
         K.gemm(y, p["fc1"].w_c, h, M=M, N=F, K=C, lda=C, ldb=p["fc1"].ld, ldc=F, bias=p["fc1"].b, act=1,

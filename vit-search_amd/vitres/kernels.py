@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import GemmArgs, LnEpilogue, RowMap, VR_BF16, VR_F32
+from ._lib import GemmArgs, LnEpilogue, RowMap, VR_BF16, VR_F16, VR_F32
 
 IDENT = (0, 0, 0)
 
@@ -20,16 +20,24 @@ PROFILE_ATTN = None       # with PROFILE: (kept FLOPs, event, event) per attenti
 PROFILE_DESC = None       # with PROFILE: one description per entry (tools/gemm_launches.py)
 
 
-def _dt(t):
-    if t.dtype == torch.float32:
-        return VR_F32
-    if t.dtype == torch.bfloat16:
-        return VR_BF16
-    raise TypeError("unsupported dtype %s" % t.dtype)
+_DTCODES = {torch.float32: VR_F32, torch.bfloat16: VR_BF16, torch.float16: VR_F16}
+_DTNAMES = {VR_F32: "f32", VR_BF16: "bf16", VR_F16: "f16"}
 
 
 def _dtcode(dtype):
-    return VR_F32 if dtype == torch.float32 else VR_BF16
+    code = _DTCODES.get(dtype)
+    if code is None:
+        raise TypeError("unsupported dtype %s (the kernels take float32, bfloat16 or float16)" % dtype)
+    return code
+
+
+def _dt(t):
+    return _dtcode(t.dtype)
+
+
+def is_fast16(dtype):
+    """The 16-bit MFMA modes (bf16; fp16 for evaluation): the dtypes whose forward takes the 16-bit kernels and their fused forms."""
+    return dtype == torch.bfloat16 or dtype == torch.float16
 
 
 def _p(t):
@@ -114,7 +122,7 @@ def _gemm_args(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=Fals
                ring=0, k_shares=0, m_groups=None):
     args = GemmArgs()
     if isinstance(ws, str):         # "auto": the role's workspace wherever the K-split kernels (gemm_ntk.hip) could be chosen
-        ws = _workspace(a.device) if (not a_trans and a.dtype == torch.bfloat16 and a.is_cuda and K >= 512 and k_shares != 1) else None
+        ws = _workspace(a.device) if (not a_trans and is_fast16(a.dtype) and a.is_cuda and K >= 512 and k_shares != 1) else None
     if ws is not None:
         args.ws, args.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
     args.ring, args.k_shares = ring, (k_shares or (K_SHARES if not a_trans else 0))
@@ -137,8 +145,8 @@ def _gemm_args(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=Fals
 
 
 def gemm_ln_supported(a, N, ldc):
-    """vr_gemm_ln covers this Linear (bf16 operands, whole rows in one tile)."""
-    return a.dtype == torch.bfloat16 and N == ldc and bool(_lib.lib().vr_gemm_ln_supported(N))
+    """vr_gemm_ln covers this Linear (16-bit operands, whole rows in one tile)."""
+    return is_fast16(a.dtype) and N == ldc and bool(_lib.lib().vr_gemm_ln_supported(N))
 
 
 def _kept_flops(M, N, K, rows_in, keep_k, keep_n, k_period=0):
@@ -173,17 +181,18 @@ def _launch_gemm_ln(args, ln, a, M, N, K, rows_in, keep_k, keep_n, k_period, ext
         a_bytes, k_w = float((rows_in * kk).sum()) * 2, float(kk.max())
     else:
         a_bytes, k_w = float(M) * K * 2, float(K)
-    PROFILE.append((("bf16", 0, 0, 2), flops, 2.0 * M * N * K, a_bytes + N * k_w * 2 + extra_bytes, e0, e1))
+    PROFILE.append(((_DTNAMES[args.in_dtype], 0, 0, 2), flops, 2.0 * M * N * K, a_bytes + N * k_w * 2 + extra_bytes, e0, e1))
     if PROFILE_DESC is not None:
         PROFILE_DESC.append("ln%d M%d N%d K%d" % (ln.mode, M, N, K))
 
 
 def gemm_ln_fwd(a, b, out, ln_w, ln_b, ln_keep, eps, *, M, N, K, lda, ldb, ldc, bias=None, scale=None, keep_n=None,
                 resid=None, rows_in=0, keep_k=None, k_period=0, sched=0):
-    """out = resid + scale * mask(a @ b^T + bias) (fp32) and (y, mean, rstd) = masked LayerNorm(out) -- vr_gemm_ln mode 0."""
+    """out = resid + scale * mask(a @ b^T + bias) (fp32) and (y, mean, rstd) = masked LayerNorm(out) -- vr_gemm_ln mode 0; y in a's
+    (16-bit) dtype."""
     args = _gemm_args(a, b, out, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, bias=bias, scale=scale, keep_n=keep_n, resid=resid,
                       rows_in=rows_in, keep_k=keep_k, k_period=k_period, sched=sched)
-    y = torch.empty(out.shape, dtype=torch.bfloat16, device=out.device)
+    y = torch.empty(out.shape, dtype=a.dtype, device=out.device)
     mean = torch.empty(M, dtype=torch.float32, device=out.device)
     rstd = torch.empty(M, dtype=torch.float32, device=out.device)
     ln = LnEpilogue()
@@ -266,7 +275,7 @@ def gemm(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=False, out
                       bias_grad=bias_grad, keep_k=keep_k, n_period=n_period, k_period=k_period, sched=sched, ws=ws,
                       ring=ring, k_shares=k_shares, m_groups=m_groups)
     if DBG_POISON and (args.sched & SKIP_WRITES_BIT) and keep_n is not None and not a_trans and resid is None and \
-            out.dtype == torch.bfloat16:
+            is_fast16(out.dtype):
         out.fill_(float("nan"))
         if out2 is not None:
             out2.fill_(float("nan"))
@@ -280,7 +289,7 @@ def gemm(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=False, out
     e0.record()
     _lib.check(_lib.lib().vr_gemm(ctypes.byref(args), _stream()), "vr_gemm")
     e1.record()
-    PROFILE.append((("bf16" if args.in_dtype == VR_BF16 else "f32", int(a_trans), int(b_trans),
+    PROFILE.append(((_DTNAMES[args.in_dtype], int(a_trans), int(b_trans),
                      int(a_map is not None or b_map is not None)), flops, 2.0 * M * N * K, alg_bytes, e0, e1))
     if PROFILE_DESC is not None:
         PROFILE_DESC.append("%s M%d N%d K%d%s%s%s%s%s%s%s" % (
@@ -312,7 +321,7 @@ def gemm_group(calls):
     _lib.check(_lib.lib().vr_gemm_group(arr, len(calls), _stream()), "vr_gemm_group")
     e1.record()
     a0, kw0 = calls[0][0], calls[0][3]
-    PROFILE.append((("bf16" if a0.dtype == torch.bfloat16 else "f32", int(kw0.get("a_trans", False)),
+    PROFILE.append(((_DTNAMES[_dt(a0)], int(kw0.get("a_trans", False)),
                      int(kw0.get("b_trans", False)), 0), flops, dense, alg, e0, e1))
     if PROFILE_DESC is not None:
         PROFILE_DESC.append("group " + " + ".join("M%d N%d K%d" % (kw["M"], kw["N"], kw["K"]) for _, _, _, kw in calls))
@@ -430,6 +439,16 @@ def copy_i32_from_pinned(host, dst):
 def cast_bf16(src, dst):
     _lib.check(_lib.lib().vr_cast_f32_bf16(_p(src), _p(dst), src.numel(), _stream()), "vr_cast_f32_bf16")
     return dst
+
+
+def cast_f16(src, dst):
+    _lib.check(_lib.lib().vr_cast_f32_f16(_p(src), _p(dst), src.numel(), _stream()), "vr_cast_f32_f16")
+    return dst
+
+
+def cast16(src, dst):
+    """fp32 -> dst's 16-bit dtype (bf16 or fp16), round to nearest even."""
+    return cast_f16(src, dst) if dst.dtype == torch.float16 else cast_bf16(src, dst)
 
 
 def tr_descs(entries, device):
@@ -641,7 +660,7 @@ def im2col3x3(a, B, H, W, C):
 
 
 def conv3x3_supported(a, Cin, Cout):
-    return a.dtype == torch.bfloat16 and Cin in (16, 24, 32) and Cout <= 32 and Cout % 4 == 0
+    return is_fast16(a.dtype) and Cin in (16, 24, 32) and Cout <= 32 and Cout % 4 == 0
 
 
 def conv3x3(a, w, B, H, W, Cin, Cout, out_dtype):
@@ -688,7 +707,7 @@ def bn_finalize(sq, n, bn, momentum, update_running):
 
 
 def conv1_direct_supported(img, w, Cout):
-    return img.dtype == torch.float32 and img.shape[1] == 3 and w.dtype == torch.bfloat16 and w.shape[1] == 32 and \
+    return img.dtype == torch.float32 and img.shape[1] == 3 and is_fast16(w.dtype) and w.shape[1] == 32 and \
         Cout <= 32 and Cout % 4 == 0
 
 

@@ -251,7 +251,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         self.num_warmup_epochs = num_warmup_epochs
         self.epoch_now = None
         self.is_supernet = supernet
-        self.compute_dtype = torch.bfloat16          # fast mode; torch.float32 = exact parity mode
+        self.compute_dtype = torch.bfloat16          # fast mode; torch.float32 = exact parity mode; torch.float16 = evaluation only
         self._arena = None
         self.last_keeps = None                       # keep vectors of the last forward (call order), for tests
 
@@ -303,7 +303,17 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         if a is not None:
             a["shadow_ver"] = None
         if a is not None and a.get("shadow_ok") and a["flat"].is_cuda:
-            K.cast_bf16(a["flat"], a["shadow"])
+            self._cast_shadow(a)
+
+    def _shadow(self, a=None):
+        """The arena's 16-bit weight shadow in the compute dtype: one buffer, read as bf16 or as fp16 (the encoding it holds follows
+        set_compute_dtype, which re-casts it on a switch)."""
+        a = self._arena if a is None else a
+        return a["shadow"].view(torch.float16) if self.compute_dtype == torch.float16 else a["shadow"]
+
+    def _cast_shadow(self, a):
+        K.cast16(a["flat"], self._shadow(a))
+        a["shadow_dtype"] = self.compute_dtype
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         out = super().load_state_dict(state_dict, strict=strict, **kw)
@@ -311,9 +321,25 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         return out
 
     def set_compute_dtype(self, dtype):
-        assert dtype in (torch.float32, torch.bfloat16)
-        self.compute_dtype = dtype
+        """torch.bfloat16 (fast mode), torch.float32 (exact parity mode) or torch.float16 (evaluation only: fp16 operands with fp32
+        accumulation, as the reference's autocast evaluation; training forwards raise)."""
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("compute dtype must be torch.float32, torch.bfloat16 or torch.float16 (got %s)" % dtype)
+        prev, self.compute_dtype = self.compute_dtype, dtype
+        a = self._arena
+        if a is not None and K.is_fast16(dtype) and (prev != dtype or a.get("shadow_dtype", dtype) != dtype):
+            # the shadow holds the other 16-bit encoding: re-cast it now (an optimizer that keeps it -- shadow_ok -- then finds it valid)
+            a["shadow_ver"] = None
+            if a["flat"].is_cuda:
+                self._cast_shadow(a)
+            else:
+                a["shadow_ok"] = False
+        self._stem_fold = None
         return self
+
+    def _check_fp16_eval(self, training):
+        if training and self.compute_dtype == torch.float16:
+            raise NotImplementedError("fp16 is eval-only; train in bf16 or fp32")
 
     def channel_drops_in_call_order(self):
         out = [self.embed_channel_drop] if self.embed_channel_drop is not None else []
@@ -347,7 +373,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         # GEMMs read the forward's weight itself (vr_gemm b_trans on the LDS-DMA kernel: k-major weight slices, transposing LDS
         # reads); only the Linears whose data gradient runs inside vr_gemm_ln (qkv / fc1 of the narrow first stage) still get a
         # transposed copy.
-        if self.compute_dtype == torch.bfloat16:
+        if K.is_fast16(self.compute_dtype):       # (backward only: bf16 whatever the 16-bit mode the arena is made in)
             entries, tot_t = [], 0
             for name, mod in self.named_modules():
                 fused = (name.endswith("attn.qkv") or name.endswith("mlp.fc1")) and isinstance(mod, nn.Linear) and \
@@ -372,7 +398,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         if self.compute_dtype == torch.float32:
             return p.detach().view(rows, -1)
         off, n = a["offsets"][a["index"][id(p)]]
-        return a["shadow"][off:off + n].view(rows, -1)
+        return self._shadow(a)[off:off + n].view(rows, -1)
 
     def _lin(self, m, wkey=None):
         w = self._wc(m.weight)
@@ -546,7 +572,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             dims_ok = self._skippable_dims = (ok, widest)
         ok, widest = dims_ok
         tokens = self.pos_embed.shape[1]                                   # (the first stage's: later stages have fewer)
-        return ok and B * tokens * widest * 2 < 0xfff00000 and self.compute_dtype == torch.bfloat16
+        return ok and B * tokens * widest * 2 < 0xfff00000 and K.is_fast16(self.compute_dtype)
 
     def _dp_scales_host(self, plan):
         """DropPath scales floor(keep_prob + u) / keep_prob (nets/drop.py:21-26) of one forward, [n_dp, B] float32 on the host in
@@ -659,6 +685,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
 
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, x, patch_output_type=None, plan=None):
+        self._check_fp16_eval(self.training)
         if _REQUIRE_CUDA and not x.is_cuda:
             raise RuntimeError('vitres runs on MI355X through libvitres_hip.so only; got a %s tensor '
                                '(the CPU restatement lives in oracle/ and is test infrastructure)' % x.device)
@@ -695,6 +722,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         logit gradients in the layout the head's backward GEMMs read.  Same gradients as `loss.backward()` on forward()'s
         outputs; they land in the flat arena and are exposed as `p.grad`.  Requires zero_grad(set_to_none=True) since the last
         backward.  Returns the loss as a 0-d device tensor (loss_out: a preallocated fp32 [1] buffer, e.g. under hipGraph capture)."""
+        self._check_fp16_eval(True)
         if _REQUIRE_CUDA and not x.is_cuda:
             raise RuntimeError('vitres runs on MI355X through libvitres_hip.so only; got a %s tensor' % x.device)
         if not self.training:
@@ -773,8 +801,8 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             else:
                 ld = (k + 7) // 8 * 8
                 wc = self._arena.get("embed_wc")            # persistent: the pad columns stay zero, one cast-copy per forward
-                if wc is None or wc.shape != (w.shape[0], ld) or wc.device != w.device:
-                    wc = self._arena["embed_wc"] = torch.zeros((w.shape[0], ld), dtype=torch.bfloat16, device=w.device)
+                if wc is None or wc.shape != (w.shape[0], ld) or wc.device != w.device or wc.dtype != self.compute_dtype:
+                    wc = self._arena["embed_wc"] = torch.zeros((w.shape[0], ld), dtype=self.compute_dtype, device=w.device)
                 K.relayout(w.detach(), wc, w.shape[0], 1, k, dst_ld=ld)             # fp32 [out, 588] -> bf16 [out, 592], pads stay zero
             return {"proj": Fn.Weights(w, pe.proj.bias.detach(), wc, ld), "pos": self.pos_embed.detach(),
                     "tokens": self.tokens.detach()}
@@ -792,7 +820,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         a = self._arena
         if save and Fn.reset_ln_grads(self) and a.get("ln_parts_flat") is not None:      # (a backward died: see _run_backward)
             a["ln_parts_flat"].zero_()
-        if self.compute_dtype == torch.bfloat16:
+        if K.is_fast16(self.compute_dtype):
             if Fn.OVERLAP and a["flat"].is_cuda:
                 Fn.join_side()             # a previous forward's side work (if its backward never ran)
             # the bf16 weight shadow: vitres.optim.FlatAdamW writes it with every update (shadow_ok).  Otherwise it is re-cast per
@@ -801,8 +829,8 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             # load_state_dict, EMA copies; raw `.data` arithmetic is not seen: call invalidate_shadow() after such edits)
             if not a.get("shadow_ok"):
                 ver = None if self.training else sum(p_._version for p_ in a["params"])
-                if ver is None or a.get("shadow_ver") != ver:
-                    K.cast_bf16(a["flat"], a["shadow"])
+                if ver is None or a.get("shadow_ver") != ver or a.get("shadow_dtype") != self.compute_dtype:
+                    self._cast_shadow(a)
                 a["shadow_ver"] = ver
         B = x.shape[0]
         tape = [] if save else None

@@ -91,7 +91,7 @@ def drop_fold(model):
 
 
 def _folded_params(model):
-    """bf16 [(w1', t1), (w2', t2), (w3', t3)] with BatchNorm folded in.  Cached between evaluation forwards; the cache is dropped
+    """Compute-dtype [(w1', t1), (w2', t2), (w3', t3)] with BatchNorm folded in.  Cached between evaluation forwards; the cache is dropped
     by drop_fold() -- Tensor._version alone is NOT a valid key: FlatAdamW updates the parameters through raw pointers and a
     replayed hipGraph updates the running statistics without touching either version counter (both are still compared, for
     in-place edits through torch)."""
@@ -99,8 +99,9 @@ def _folded_params(model):
     convs = (pe.conv1, pe.conv2, pe.conv3)
     ver = tuple(t._version for c in convs for t in (c.conv.weight, c.bn.weight, c.bn.bias, c.bn.running_mean, c.bn.running_var))
     ptr = tuple(c.conv.weight.data_ptr() for c in convs)
+    dt = model.compute_dtype                     # (bf16 / fp16: the operand type of the folded convolutions; cached per dtype)
     cache = getattr(model, "_stem_fold", None)
-    if cache is not None and cache[0] == (ver, ptr):
+    if cache is not None and cache[0] == (ver, ptr, dt):
         return cache[1]
     out = []
     for i, c in enumerate(convs):
@@ -111,10 +112,10 @@ def _folded_params(model):
         o, k = w.shape[0], w.shape[1] * w.shape[2] * w.shape[3]
         wp = w.permute(0, 2, 3, 1).reshape(o, k) * scale[:, None]
         ld = 32 if i == 0 else k
-        wf = torch.zeros((o, ld), dtype=torch.bfloat16, device=w.device)
+        wf = torch.zeros((o, ld), dtype=dt, device=w.device)
         wf[:, :k] = wp
         out.append((wf, shift))
-    model._stem_fold = ((ver, ptr), out)
+    model._stem_fold = ((ver, ptr, dt), out)
     return out
 
 
@@ -151,7 +152,7 @@ def _embed_conv_eval(model, x, p, cfg, keep):
 
 def embed_conv_fwd(model, x, p, cfg, keep, save):
     pe, dt = model.patch_embed, cfg["dtype"]
-    if FOLD_BN and not save and not model.training and dt == torch.bfloat16 and K.conv3x3_supported(x.new_empty(0, dtype=dt), pe.mid_chans, pe.mid_chans):
+    if FOLD_BN and not save and not model.training and K.is_fast16(dt) and K.conv3x3_supported(x.new_empty(0, dtype=dt), pe.mid_chans, pe.mid_chans):
         return _embed_conv_eval(model, x, p, cfg, keep)
     B, _, H, W = x.shape
     m, C, P = pe.mid_chans, cfg["dim"], cfg["patches"]
