@@ -269,6 +269,39 @@ int vr_adamw_flat_dev_capped(float* p, const float* g, float* m, float* v, void*
                              const uint8_t* group_of_8, const vr_adamw_group* groups_dev, int32_t n_groups, int64_t n,
                              int32_t max_blocks, vr_stream_t stream);
 
+/*
+ * Gradient-norm clipping on the device (torch.nn.utils.clip_grad_norm_, the reference's `--clip-grad`: loss_scaler(...,
+ * clip_grad=max_norm), engine.py:178-180), in front of the AdamW pass and capturable into the same hipGraph:
+ *   vr_grad_sumsq (one launch per finished arena range)  ->  vr_clip_finish  ->  vr_adamw_flat_clip
+ * Stream order is the only synchronisation between the three.  vr_clip_state lives in DEVICE memory: the caller writes max_norm
+ * (+inf: measure only) and grad_scale (the factor AdamW applies to every gradient) before a step; vr_clip_finish writes the rest:
+ *   norm = grad_scale * sqrt(sum of squares)          the norm of the gradient the optimizer uses, before clipping
+ *   coef = min(1, max_norm / (norm + 1e-6))           torch's formula
+ *   skip = 1 if norm is inf or NaN (coef is 0 then), skipped += 1 in that case (a running count the caller zeroes once).
+ */
+typedef struct vr_clip_state {
+    float max_norm, grad_scale;   /* in  */
+    float norm, coef;             /* out */
+    int32_t skip, skipped;        /* out */
+    int32_t reserved[2];
+} vr_clip_state;
+/* Sum of g[i]^2 over the elements of [0, n) whose group byte is not 255 (g, group_of_8 as for vr_adamw_flat_dev: a range of the
+ * arena, group_of_8 advanced by offset / 8; n % 8 == 0).  Launches exactly n_partials workgroups of 256 threads; workgroup b writes
+ * partials[b] (plain store, 0 if it had no work), so nothing needs zeroing and equal inputs give equal bits.  At most
+ * min(n_partials, max_blocks if > 0, ceil(n / 2048)) workgroups share the range (grid-stride, 8 elements per thread and trip, eight
+ * independent fp32 accumulators per thread): choose n_partials so that n / (2048 * n_partials) stays <= 256 trips.  Several
+ * launches may fill disjoint slices of one partials buffer. */
+int vr_grad_sumsq(const float* g, const uint8_t* group_of_8, int64_t n, float* partials, int32_t n_partials,
+                  int32_t max_blocks, vr_stream_t stream);
+/* One workgroup: sums partials[0 .. n_partials) in double precision and fills the output half of *state (see above). */
+int vr_clip_finish(const float* partials, int32_t n_partials, vr_clip_state* state, vr_stream_t stream);
+/* vr_adamw_flat (groups_on_device == 0: `groups` in host memory) or vr_adamw_flat_dev_capped (!= 0: in device memory) with the
+ * gradient g * grad_scale * clip->coef; if clip->skip is set the launch writes nothing: parameters, both moments, EMA and shadow
+ * stay as they were.  max_blocks as for vr_adamw_flat_dev_capped (0: the default grid). */
+int vr_adamw_flat_clip(float* p, const float* g, float* m, float* v, void* shadow, float* ema, float ema_decay,
+                       const uint8_t* group_of_8, const vr_adamw_group* groups, int32_t groups_on_device, int32_t n_groups,
+                       int64_t n, const vr_clip_state* clip, int32_t max_blocks, vr_stream_t stream);
+
 
 /*
  * Masked LayerNorm forward (nets/masked_layer_norm.py:23-50,113-125).  x fp32 [M,C] -> y (dtype) [M,C];

@@ -66,6 +66,9 @@ SYMBOLS = {
     "vr_adamw_flat": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_void_p],
     "vr_adamw_flat_dev": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_void_p],
     "vr_adamw_flat_dev_capped": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p],
+    "vr_grad_sumsq": [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p],
+    "vr_clip_finish": [c_void_p, c_int32, c_void_p, c_void_p],
+    "vr_adamw_flat_clip": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p],
     "vr_cast_transpose_batch": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
     "vr_ln_fwd": [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_float, c_int32, c_void_p],
     "vr_ln_bwd": [c_void_p] * 13 + [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],

@@ -218,7 +218,11 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
     """One optimisation step; returns the loss tensor (on device, not synchronised).  average_grads=False leaves the
     all-reduced SUM in the arena (optimizer applies 1/world: vitres.optim.FlatAdamW.grad_scale).  teacher_output +
     kd_criterion: knowledge distillation, loss = (1 - alpha) * criterion(cls) + alpha * kd(dst, teacher) (engine.py:135-148;
-    a one-token model distils through its class logits, as the reference's `output_dst = outputs`)."""
+    a one-token model distils through its class logits, as the reference's `output_dst = outputs`).
+    max_norm (reference: loss_scaler(..., clip_grad=max_norm), engine.py:178-180) without a loss_scaler: a vitres.optim.FlatAdamW
+    clips on the device inside its own step (optimizer.max_norm is set to it: vr_grad_sumsq -> vr_clip_finish ->
+    vr_adamw_flat_clip; optimizer.grad_norm() holds the norm afterwards); any other optimizer gets
+    torch.nn.utils.clip_grad_norm_.  Either way after the all-reduce, so every rank clips the same averaged gradients."""
     rng = None
     if arch_sample is not None:                                   # engine.py:119-131
         rng = torch.random.get_rng_state()
@@ -264,7 +268,9 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
         loss.backward()
         if grad_sync is not None:
             grad_sync.all_reduce_grads(average=average_grads)
-        if max_norm:
+        if max_norm and hasattr(optimizer, "clip_enabled"):       # FlatAdamW: one clipping path per optimizer type
+            optimizer.max_norm = max_norm
+        elif max_norm:
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
         optimizer.step()
     return loss.detach()
@@ -291,7 +297,11 @@ class GraphedTrainStep:
         step_with_sync() can all-reduce the finished tail of the gradient arena (most of the parameters) while the rest
         of the backward -- most of the time -- is still running.
         opt_overlap / opt_overlap_blocks (with optimizer): number of arena ranges updated early, beside the rest of the backward,
-        and the workgroup cap of those updates (see below)."""
+        and the workgroup cap of those updates (see below).  With optimizer.max_norm set at capture no parameter may change before
+        the whole gradient norm is known: the early launches then are the SUMS OF SQUARES of those ranges (same stream, ranges and
+        cap), and the remaining range's sum, the finish and ONE full-width AdamW follow the backward.  The replays follow
+        optimizer.max_norm from value to value (float("inf"): measure only); switching it on or off after the capture makes
+        optimizer.prepare_step() raise."""
         if hasattr(model, "_check_fp16_eval"):
             model._check_fp16_eval(True)          # (fp16 is an evaluation mode: nothing is captured or launched)
         self.model, self.criterion, self.pot = model, criterion, patch_output_type
@@ -356,9 +366,15 @@ class GraphedTrainStep:
         try:
             self._loss_buf = torch.zeros(1, dtype=torch.float32, device=samples.device)
             opt_cut = None
+            clip = False
             if self.optimizer is not None:
+                clip = bool(getattr(self.optimizer, "clip_enabled", lambda: False)())
+                self.optimizer._graph_clip = None
                 self.optimizer.prepare_step()                      # allocates / fills the device hyper-parameters (not captured)
                 self.optimizer._step -= 1
+                self.optimizer._graph_clip = clip                  # (prepare_step() raises once max_norm no longer matches)
+                if clip:
+                    self.optimizer._clip["used"] = 0
                 # opt_overlap = number of arena ranges updated EARLY (0 off, 1 (default): head + last stage, 2: + the stage
                 # before; measured round 4: 7.47 -> 7.36 - 7.39 ms with 1 or 2, profiles/r04_optimizer_overlap.txt):
                 # the backward is cut in front of the spatial reductions (model.split_plan) and the range a part completes is
@@ -384,16 +400,29 @@ class GraphedTrainStep:
                     if opt_cut is not None and getattr(model, "_bwd_state", None) is not None:
                         hi = n_arena
                         for _, lo in opt_cut:                          # ranges complete from the arena's end backwards
-                            if Fn.OVERLAP:
-                                Fn.on_side(lambda lo=lo, hi=hi: self.optimizer.step_device(lo, hi, max_blocks=opt_overlap_blocks))
+                            if clip:                                   # (each range fills its own slice of the partial sums)
+                                piece = self.optimizer.reserve_norm_slice(lo, hi)
+                                early = lambda lo=lo, hi=hi, piece=piece, cap=opt_overlap_blocks if Fn.OVERLAP else 0: \
+                                    self.optimizer.norm_range_device(lo, hi, piece, max_blocks=cap)       # noqa: E731
                             else:
-                                self.optimizer.step_device(lo, hi)
+                                early = lambda lo=lo, hi=hi, cap=opt_overlap_blocks if Fn.OVERLAP else 0: \
+                                    self.optimizer.step_device(lo, hi, max_blocks=cap)                    # noqa: E731
+                            if Fn.OVERLAP:
+                                Fn.on_side(early)
+                            else:
+                                early()
                             hi = lo
                             if getattr(model, "_bwd_state", None) is not None:
                                 model.resume_backward()
-                        self.optimizer.step_device(0, hi)
                     else:
-                        self.optimizer.step_device(0, n_arena)
+                        hi = n_arena
+                    if clip:
+                        # the last backward part joined the side stream: every early sum is complete in stream order
+                        self.optimizer.norm_range_device(0, hi, self.optimizer.reserve_norm_slice(0, hi))
+                        self.optimizer.clip_finish_device()
+                        self.optimizer.step_device(0, n_arena, clip=True)
+                    else:
+                        self.optimizer.step_device(0, hi)
             while getattr(model, "_bwd_state", None) is not None:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=self.graph.pool()):
@@ -441,6 +470,10 @@ class GraphedTrainStep:
     def __call__(self, samples, targets, patch_targets=None, epoch=0, train_iter=0, arch_sample=None):
         if hasattr(self.model, "_check_fp16_eval"):
             self.model._check_fp16_eval(True)     # (the model was switched to fp16 after the capture: no replay)
+        if self.optimizer is not None and getattr(self.optimizer, "_graph_clip", None) is not None and \
+                self.optimizer.clip_enabled() != self.optimizer._graph_clip:
+            raise RuntimeError("optimizer.max_norm was switched %s after this step's graph was captured: the replay would ignore it"
+                               % ("on" if self.optimizer.clip_enabled() else "off"))
         rng = None
         if arch_sample is not None:                                # engine.py:119-131
             rng = torch.random.get_rng_state()

@@ -5,6 +5,11 @@ Reference: timm 0.3.2 `create_optimizer(args, model)` -> torch.optim.AdamW(lr, w
 `FlatAdamW` keeps torch.optim.Optimizer's interface (param_groups with mutable 'lr' for the cosine scheduler,
 state_dict / load_state_dict, zero_grad) but its state is two flat fp32 buffers shaped like the model's arena, and step()
 is one `vr_adamw_flat` launch that also refreshes the bf16 weight shadow the next forward reads.
+
+Gradient-norm clipping (the reference's `--clip-grad`: loss_scaler(loss, optimizer, clip_grad=max_norm, ...), engine.py:178-180, i.e.
+torch.nn.utils.clip_grad_norm_) is part of the same tail when `max_norm` is set: vr_grad_sumsq over the gradient arena ->
+vr_clip_finish (norm, coefficient, skip flag in a device-resident vr_clip_state) -> vr_adamw_flat_clip, which multiplies every
+gradient by the coefficient.  All three are capturable (engine.GraphedTrainStep).
 """
 import ctypes
 import math
@@ -15,6 +20,10 @@ from . import _lib
 from .kernels import _p, _stream
 
 MAX_GROUPS = 16
+# vr_grad_sumsq: partial sums per arena range (one per workgroup) and ranges per step.  2048 workgroups of 256 threads at 8 elements
+# per trip keep every thread's fp32 chains at 144 M / (2048 * 2048) = 35 terms for the largest shipped arena (bound: 256).
+NORM_PARTIALS = 2048
+NORM_MAX_RANGES = 8
 
 
 class _Group(ctypes.Structure):
@@ -22,11 +31,33 @@ class _Group(ctypes.Structure):
                                               "grad_scale")]
 
 
+class _ClipState(ctypes.Structure):            # vr_clip_state (include/vitres_hip.h): 8 dwords
+    _fields_ = [("max_norm", ctypes.c_float), ("grad_scale", ctypes.c_float), ("norm", ctypes.c_float), ("coef", ctypes.c_float),
+                ("skip", ctypes.c_int32), ("skipped", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+def _check_max_norm(v):
+    if v is None:
+        return None
+    v = float(v)
+    if math.isnan(v) or v < 0:
+        raise ValueError("max_norm must be None, 0 (both: no clipping), a positive number or inf (measure only), got %r" % v)
+    return v
+
+
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, model, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None):
+    def __init__(self, model, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None, max_norm=None):
         """params: iterable of parameters or of param-group dicts (as torch.optim.AdamW); every parameter must belong to
         `model`, whose arena they live in.  ema_decay: keep an exponential moving average of the parameters
-        (`ema_state_dict()` returns it under the model's state_dict keys)."""
+        (`ema_state_dict()` returns it under the model's state_dict keys).
+        max_norm: clip the global L2 norm of the gradients (of all groups together, after grad_scale) to this value before the
+        update, as torch.nn.utils.clip_grad_norm_ does: every gradient is multiplied by min(1, max_norm / (norm + 1e-6)).  A plain
+        attribute that may change between steps.  None or 0: off -- no extra launch, no extra allocation.  float("inf"): the norm
+        is measured (grad_norm()) and non-finite steps are skipped, nothing is clipped.  While it is on, a step whose gradient
+        norm is inf or NaN changes NOTHING on the device -- parameters, moments, EMA and bf16 shadow keep their values
+        (skipped_steps() counts them) -- where torch's formula would turn every parameter into NaN.  The host step count still
+        advances on such a step: the host runs ahead of the device and cannot know.  Against torch.cuda.amp.GradScaler, which does
+        not count a skipped step, only the bias corrections of the later steps differ (they are one step further along)."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) > MAX_GROUPS:
             raise ValueError("at most %d parameter groups" % MAX_GROUPS)
@@ -35,6 +66,82 @@ class FlatAdamW(torch.optim.Optimizer):
         self._step = 0
         self._arena_id = None
         self.grad_scale = 1.0              # e.g. 1/world when the all-reduce leaves a SUM in the gradient arena
+        self.max_norm = _check_max_norm(max_norm)
+        self._clip = None                  # device state of the clipping launches: allocated by the first step that clips
+        self._graph_clip = None            # engine.GraphedTrainStep: whether its captured graph holds the clipping launches
+
+    # ---- gradient-norm clipping ---------------------------------------------------------------------------------
+    def clip_enabled(self):
+        return bool(_check_max_norm(self.max_norm))
+
+    def _clip_bind(self, dev):
+        c = self._clip
+        if c is None or c["state"].device != dev:
+            old = c
+            c = self._clip = {"state": torch.zeros(8, dtype=torch.float32, device=dev),
+                              "partials": torch.zeros(NORM_PARTIALS * NORM_MAX_RANGES, dtype=torch.float32, device=dev), "used": 0}
+            c["state"][2:4] = torch.tensor([0.0, 1.0])     # (norm, coef) before the first measured step
+            if old is not None:
+                c["state"].copy_(old["state"])
+        return c
+
+    def _clip_upload(self, dev, pinned=False):
+        """max_norm and grad_scale -> the input half of the device's vr_clip_state (the output half is the device's own)."""
+        c = self._clip_bind(dev)
+        host = torch.tensor([_check_max_norm(self.max_norm), float(self.grad_scale)], dtype=torch.float32)
+        if pinned and dev.type == "cuda":
+            host = host.pin_memory()       # (a fresh block per step, as for the hyper-parameters in prepare_step)
+        c["state"][:2].copy_(host, non_blocking=pinned)
+        return c
+
+    def reserve_norm_slice(self, lo, hi):
+        """The slice of the partial-sum buffer norm_range_device(lo, hi) will fill: (first, count).  Slices are handed out in
+        call order and given back by clip_finish_device()."""
+        c = self._clip_bind(self._bind()["flat"].device)
+        count = min(((hi - lo) // 8 + 255) // 256, NORM_PARTIALS)
+        if c["used"] + count > c["partials"].numel():
+            raise RuntimeError("more than %d arena ranges in one gradient norm" % NORM_MAX_RANGES)
+        first, c["used"] = c["used"], c["used"] + count
+        return first, count
+
+    @torch.no_grad()
+    def norm_range_device(self, lo, hi, piece, max_blocks=0):
+        """Sum of squares of the gradient arena range [lo, hi) (multiples of 8) into the slice `piece` = reserve_norm_slice(lo,
+        hi) of the partial sums: capturable.  max_blocks as for step_device."""
+        a = self._bind()
+        g = a.get("gcur")
+        n = a["flat"].numel()
+        if g is None:
+            raise RuntimeError("norm_range_device needs gradients in the arena")
+        if lo % 8 or hi % 8 or not (0 <= lo < hi <= n):
+            raise ValueError("range must be non-empty and aligned to 8 elements")
+        c = self._clip_bind(a["flat"].device)
+        first, count = piece
+        if not (0 <= first and count > 0 and first + count <= c["partials"].numel()):
+            raise ValueError("piece is not a slice of the partial-sum buffer")
+        _lib.check(_lib.lib().vr_grad_sumsq(g.data_ptr() + 4 * lo, self._flat_state["gid"].data_ptr() + lo // 8, hi - lo,
+                                            c["partials"].data_ptr() + 4 * first, count, int(max_blocks), _stream()),
+                   "vr_grad_sumsq")
+
+    @torch.no_grad()
+    def clip_finish_device(self):
+        """Partial sums of every norm_range_device since the last call -> norm, clip coefficient and skip flag on the device."""
+        c = self._clip
+        if c is None or c["used"] == 0:
+            raise RuntimeError("clip_finish_device needs norm_range_device launches before it")
+        _lib.check(_lib.lib().vr_clip_finish(_p(c["partials"]), c["used"], _p(c["state"]), _stream()), "vr_clip_finish")
+        c["used"] = 0
+
+    def grad_norm(self):
+        """L2 norm of the last step's gradient as the optimizer used it (after grad_scale, before clipping), as clip_grad_norm_
+        returns it: a 0-dim device tensor, not synchronised.  Needs max_norm (float("inf") measures without clipping)."""
+        if self._clip is None:
+            raise RuntimeError("grad_norm() needs max_norm set (float('inf') measures without clipping) and one step taken")
+        return self._clip["state"][2]
+
+    def skipped_steps(self):
+        """Number of steps skipped so far because their gradient norm was inf or NaN (synchronises)."""
+        return 0 if self._clip is None else int(self._clip["state"].view(torch.int32)[5].item())
 
     # ---- arena-shaped state -------------------------------------------------------------------------------
     def _bind(self):
@@ -75,9 +182,18 @@ class FlatAdamW(torch.optim.Optimizer):
         arr = self._group_structs(self._step)
         st = self._flat_state
         shadow = a["shadow"] if self.model.compute_dtype == torch.bfloat16 else None
-        _lib.check(_lib.lib().vr_adamw_flat(_p(a["flat"]), _p(g), _p(st["m"]), _p(st["v"]), _p(shadow), _p(st["ema"]),
-                                            float(self.ema_decay or 0.0), _p(st["gid"]), ctypes.byref(arr),
-                                            len(self.param_groups), a["flat"].numel(), _stream()), "vr_adamw_flat")
+        if self.clip_enabled():            # sum of squares -> norm / coefficient -> AdamW on the clipped gradient: three launches
+            n = a["flat"].numel()
+            c = self._clip_upload(a["flat"].device)
+            self.norm_range_device(0, n, self.reserve_norm_slice(0, n))
+            self.clip_finish_device()
+            _lib.check(_lib.lib().vr_adamw_flat_clip(_p(a["flat"]), _p(g), _p(st["m"]), _p(st["v"]), _p(shadow), _p(st["ema"]),
+                                                     float(self.ema_decay or 0.0), _p(st["gid"]), ctypes.byref(arr), 0,
+                                                     len(self.param_groups), n, _p(c["state"]), 0, _stream()), "vr_adamw_flat_clip")
+        else:
+            _lib.check(_lib.lib().vr_adamw_flat(_p(a["flat"]), _p(g), _p(st["m"]), _p(st["v"]), _p(shadow), _p(st["ema"]),
+                                                float(self.ema_decay or 0.0), _p(st["gid"]), ctypes.byref(arr),
+                                                len(self.param_groups), a["flat"].numel(), _stream()), "vr_adamw_flat")
         if shadow is not None:
             a["shadow_ok"] = True              # forwards skip their own vr_cast_f32_bf16 from now on (model.invalidate_shadow)
         return loss
@@ -94,7 +210,14 @@ class FlatAdamW(torch.optim.Optimizer):
     def prepare_step(self):
         """Advance the step count and upload this step's per-group hyper-parameters (learning rates written by the scheduler,
         bias corrections) to the device buffer step_device() launches read -- call once before every replay of a graph that
-        contains step_device() launches (engine.GraphedTrainStep(optimizer=...))."""
+        contains step_device() launches (engine.GraphedTrainStep(optimizer=...)).  With max_norm set, max_norm and grad_scale
+        are uploaded too; a graph holds the clipping launches or not from its capture on, so switching max_norm between on and
+        off after the capture raises here (on <-> float("inf") is the switch a captured graph follows)."""
+        if self._graph_clip is not None and self.clip_enabled() != self._graph_clip:
+            raise RuntimeError("FlatAdamW.max_norm was %s after the step's graph was captured %s the clipping launches: a replay "
+                               "would ignore it.  Capture with max_norm set (float('inf') measures without clipping) and switch "
+                               "between values, or capture a new GraphedTrainStep."
+                               % (("set", "without") if self.clip_enabled() else ("cleared", "with")))
         a = self._bind()
         dev = a["flat"].device
         if getattr(self, "_hp_dev", None) is None or self._hp_dev.device != dev:
@@ -109,11 +232,15 @@ class FlatAdamW(torch.optim.Optimizer):
             host = host.pin_memory()       # a fresh pinned block per step: the host runs several replays ahead of the device, a
                                            # reused staging buffer would be overwritten before its copy has executed
         self._hp_dev.copy_(host, non_blocking=True)
+        if self.clip_enabled():
+            self._clip_upload(dev, pinned=True)
 
     @torch.no_grad()
-    def step_device(self, lo=0, hi=None, max_blocks=0):
+    def step_device(self, lo=0, hi=None, max_blocks=0, clip=False):
         """AdamW over the arena range [lo, hi) (multiples of 8) with the hyper-parameters prepare_step() uploaded: capturable.
-        max_blocks > 0: launched with at most that many workgroups (an update that runs beside other work)."""
+        max_blocks > 0: launched with at most that many workgroups (an update that runs beside other work).
+        clip: the gradient is also multiplied by the coefficient clip_finish_device() left on the device (and nothing is written
+        on a skipped step) -- the launch must follow the finish of the WHOLE arena's norm."""
         a = self._bind()
         g = a.get("gcur")
         if g is None or getattr(self, "_hp_dev", None) is None:
@@ -128,6 +255,16 @@ class FlatAdamW(torch.optim.Optimizer):
 
         def at(t, esz):
             return None if t is None else t.data_ptr() + lo * esz
+        if clip:
+            if self._clip is None:
+                raise RuntimeError("step_device(clip=True) needs clip_finish_device() before it")
+            _lib.check(_lib.lib().vr_adamw_flat_clip(at(a["flat"], 4), at(g, 4), at(st["m"], 4), at(st["v"], 4), at(shadow, 2),
+                                                     at(st["ema"], 4), float(self.ema_decay or 0.0), st["gid"].data_ptr() + lo // 8,
+                                                     _p(self._hp_dev), 1, len(self.param_groups), hi - lo, _p(self._clip["state"]),
+                                                     int(max_blocks), _stream()), "vr_adamw_flat_clip")
+            if shadow is not None:
+                a["shadow_ok"] = True
+            return
         _lib.check(_lib.lib().vr_adamw_flat_dev_capped(at(a["flat"], 4), at(g, 4), at(st["m"], 4), at(st["v"], 4), at(shadow, 2),
                                                        at(st["ema"], 4), float(self.ema_decay or 0.0), st["gid"].data_ptr() + lo // 8,
                                                        _p(self._hp_dev), len(self.param_groups), hi - lo, int(max_blocks), _stream()),
@@ -150,7 +287,8 @@ class FlatAdamW(torch.optim.Optimizer):
         st = self._flat_state
         return {"step": self._step, "exp_avg": st["m"].clone(), "exp_avg_sq": st["v"].clone(),
                 "ema": None if st["ema"] is None else st["ema"].clone(),
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+                "max_norm": _check_max_norm(self.max_norm)}
 
     def load_state_dict(self, sd):
         """Accepts its own flat layout or torch.optim.AdamW's (the 'optimizer' entry of a reference checkpoint.pth.tar,
@@ -166,6 +304,8 @@ class FlatAdamW(torch.optim.Optimizer):
             st["ema"].copy_(sd["ema"])
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update(s)
+        if "max_norm" in sd:                   # (a state dict written before max_norm existed leaves the constructor's value)
+            self.max_norm = _check_max_norm(sd["max_norm"])
 
     def _ordered_params(self):
         return [p for g in self.param_groups for p in g["params"]]      # torch numbers parameters in this order
