@@ -295,6 +295,13 @@ int vr_grad_sumsq(const float* g, const uint8_t* group_of_8, int64_t n, float* p
                   int32_t max_blocks, vr_stream_t stream);
 /* One workgroup: sums partials[0 .. n_partials) in double precision and fills the output half of *state (see above). */
 int vr_clip_finish(const float* partials, int32_t n_partials, vr_clip_state* state, vr_stream_t stream);
+/* Gated forms for gradient accumulation inside ONE captured graph: `gate` points at an int32 in device memory that the host rewrites
+ * before each replay.  Gate 0: the launch returns at once, uniformly over the grid -- vr_grad_sumsq_gated leaves its slice of the
+ * partial sums untouched, vr_clip_finish_gated every field of *state (skipped included).  Gate != 0: the ungated entry point's result,
+ * bit for bit. */
+int vr_grad_sumsq_gated(const float* g, const uint8_t* group_of_8, int64_t n, float* partials, int32_t n_partials,
+                        int32_t max_blocks, const int32_t* gate, vr_stream_t stream);
+int vr_clip_finish_gated(const float* partials, int32_t n_partials, vr_clip_state* state, const int32_t* gate, vr_stream_t stream);
 /* vr_adamw_flat (groups_on_device == 0: `groups` in host memory) or vr_adamw_flat_dev_capped (!= 0: in device memory) with the
  * gradient g * grad_scale * clip->coef; if clip->skip is set the launch writes nothing: parameters, both moments, EMA and shadow
  * stay as they were.  max_blocks as for vr_adamw_flat_dev_capped (0: the default grid). */
@@ -452,6 +459,9 @@ typedef struct vr_range_list {
     int32_t reserved;
 } vr_range_list;
 int vr_zero_ranges(float* base, const vr_range_list* ranges, vr_stream_t stream);
+/* The same behind a gate word (int32, device memory): *gate == 0 leaves the buffer untouched (the first micro-step of an update
+ * window clears the gradient arena, the others add to it; one captured graph serves all of them). */
+int vr_zero_ranges_gated(float* base, const vr_range_list* ranges, const int32_t* gate, vr_stream_t stream);
 
 /*
  * dst[a * dst_ld + c * B + b] = src[a * src_ld + b * C + c]  (dtype codes as everywhere; pad columns of dst untouched).
@@ -461,6 +471,9 @@ int vr_zero_ranges(float* base, const vr_range_list* ranges, vr_stream_t stream)
  */
 int vr_relayout(const void* src, void* dst, int32_t A, int32_t B, int32_t C, int64_t src_ld, int64_t dst_ld, int32_t src_dtype,
                 int32_t dst_dtype, vr_stream_t stream);
+/* dst[a * dst_ld + c * B + b] += src[a * src_ld + b * C + c], fp32 both sides: the same index map, adding -- the gradient writers that
+ * go through a temporary (convolution-shaped weight gradients, padded rows) under gradient accumulation.  A = B = 1: dst += src. */
+int vr_relayout_add(const float* src, float* dst, int32_t A, int32_t B, int32_t C, int64_t src_ld, int64_t dst_ld, vr_stream_t stream);
 
 /* x[m, c] = 0 for c >= keep[sample(m)]  (ChannelDrop.forward `x * mask`, nets/channel_drop.py:82) */
 int vr_mask_rows(float* x, const int32_t* keep, int32_t M, int32_t C, int32_t rows_per_sample, vr_stream_t stream);

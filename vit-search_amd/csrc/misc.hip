@@ -733,7 +733,7 @@ extern "C" int vr_sr_resid_bwd(const float* dout, float* dx, int32_t B, int32_t 
 // start at zero -- except the spans whose weight gradients are written in store form (vr_gemm atomic == 2): the ranges in
 // between are what this kernel clears (reference: optimizer.zero_grad(), engine.py:175).
 namespace {
-__global__ __launch_bounds__(256) void zero_ranges_kernel(float* base, const vr_range_list r) {
+__device__ __forceinline__ void zero_ranges_body(float* base, const vr_range_list& r) {
     const long long lo = r.lo[blockIdx.y], n = r.count[blockIdx.y];
     float* p = base + lo;
     const long long stride = (long long)gridDim.x * blockDim.x;
@@ -755,10 +755,20 @@ __global__ __launch_bounds__(256) void zero_ranges_kernel(float* base, const vr_
     const long long tail0 = head + (n4 << 2);
     if (tail0 + i < n && i < 4) p[tail0 + i] = 0.f;
 }
+
+__global__ __launch_bounds__(256) void zero_ranges_kernel(float* base, const vr_range_list r) { zero_ranges_body(base, r); }
+
+// The same fill behind a gate word in device memory: every thread of the grid reads the one word and the whole launch returns when it
+// is 0 (gradient accumulation: ONE captured graph serves every micro-step, only the first of a window clears the arena).
+__global__ __launch_bounds__(256) void zero_ranges_gated_kernel(float* base, const vr_range_list r, const int32_t* __restrict__ gate) {
+    if (*gate == 0) return;
+    zero_ranges_body(base, r);
+}
 }  // namespace
 
-extern "C" int vr_zero_ranges(float* base, const vr_range_list* ranges, vr_stream_t stream) {
-    if (!base || !ranges || ranges->n <= 0 || ranges->n > VR_MAX_ZERO_RANGES) return VR_EINVAL;
+static int zero_ranges_launch(float* base, const vr_range_list* ranges, const int32_t* gate, bool gated, vr_stream_t stream) {
+    if (!base || !ranges || ranges->n <= 0 || ranges->n > VR_MAX_ZERO_RANGES || (gated && !gate)) return VR_EINVAL;
+    if (gated && ((uintptr_t)gate & 3)) return VR_EALIGN;
     long long most = 0;
     for (int i = 0; i < ranges->n; ++i) {
         if (ranges->lo[i] < 0 || ranges->count[i] < 0) return VR_EINVAL;
@@ -767,9 +777,21 @@ extern "C" int vr_zero_ranges(float* base, const vr_range_list* ranges, vr_strea
     if (most == 0) return VR_OK;
     long long bx = (most / 16 + 255) / 256;
     bx = bx < 1 ? 1 : (bx > 4096 ? 4096 : bx);
-    hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)bx, (unsigned)ranges->n), dim3(256), 0, (hipStream_t)stream, base, *ranges);
+    if (gated)
+        hipLaunchKernelGGL(zero_ranges_gated_kernel, dim3((unsigned)bx, (unsigned)ranges->n), dim3(256), 0, (hipStream_t)stream, base, *ranges,
+                           gate);
+    else
+        hipLaunchKernelGGL(zero_ranges_kernel, dim3((unsigned)bx, (unsigned)ranges->n), dim3(256), 0, (hipStream_t)stream, base, *ranges);
     VR_CHECK_LAUNCH();
     return VR_OK;
+}
+
+extern "C" int vr_zero_ranges(float* base, const vr_range_list* ranges, vr_stream_t stream) {
+    return zero_ranges_launch(base, ranges, nullptr, false, stream);
+}
+
+extern "C" int vr_zero_ranges_gated(float* base, const vr_range_list* ranges, const int32_t* gate, vr_stream_t stream) {
+    return zero_ranges_launch(base, ranges, gate, true, stream);
 }
 
 // ---- vr_relayout: dst[a * dst_ld + c * B + b] = src[a * src_ld + b * C + c]  (fp32 / bf16 / fp16 in and out; bf16 and fp16 are not mixed) ----
@@ -813,6 +835,36 @@ extern "C" int vr_relayout(const void* src, void* dst, int32_t A, int32_t B, int
         hipLaunchKernelGGL((relayout_kernel<f16_t, float>), dim3(grid), dim3(256), 0, st, (const f16_t*)src, (float*)dst, A, B, C, src_ld, dst_ld);
     else
         return VR_EUNSUPPORTED;
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
+
+// ---- vr_relayout_add: dst[a * dst_ld + c * B + b] += src[a * src_ld + b * C + c], fp32 both sides ------------------------------------
+// The accumulate form of the re-layouts that end a convolution-shaped weight gradient (temporary [out, (taps, in)] -> the arena's
+// [out, in, taps]) and, with A = B = 1, a plain dst += src: under gradient accumulation the arena holds the earlier micro-steps' sum.
+// Every destination element has exactly one writer: a read-modify-write, no atomics.
+namespace {
+__global__ __launch_bounds__(256) void relayout_add_kernel(const float* __restrict__ src, float* __restrict__ dst, int A, int B, int C,
+                                                           long long src_ld, long long dst_ld) {
+    const long long total = (long long)A * B * C;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int b = (int)(i % B);
+        const long long r = i / B;
+        const int c = (int)(r % C);
+        const int a = (int)(r / C);
+        float* d = dst + a * dst_ld + (long long)c * B + b;
+        *d += src[a * src_ld + (long long)b * C + c];
+    }
+}
+}  // namespace
+
+extern "C" int vr_relayout_add(const float* src, float* dst, int32_t A, int32_t B, int32_t C, int64_t src_ld, int64_t dst_ld,
+                               vr_stream_t stream) {
+    if (!src || !dst || A <= 0 || B <= 0 || C <= 0 || dst_ld < (int64_t)B * C || src_ld < (int64_t)B * C) return VR_EINVAL;
+    if (((uintptr_t)src & 3) || ((uintptr_t)dst & 3)) return VR_EALIGN;
+    const long long total = (long long)A * B * C;
+    const unsigned grid = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(relayout_add_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, dst, A, B, C, src_ld, dst_ld);
     VR_CHECK_LAUNCH();
     return VR_OK;
 }

@@ -85,8 +85,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 // launch beside the backward) write 0.  Nothing is accumulated across launches: no zeroing, no atomics, the same bits every replay.
 // Error: eight independent fp32 chains per thread (one per element of a group of 8), each n8 / (active * 256) terms long, then
 // a tree: 3 levels in the thread, 6 in the wave, 2 across the waves.
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, const uint8_t* __restrict__ group_of_8, long long n8,
-                                                    int active, float* __restrict__ partials) {
+__device__ __forceinline__ void sumsq_body(const float* __restrict__ g, const uint8_t* __restrict__ group_of_8, long long n8, int active,
+                                           float* __restrict__ partials) {
     __shared__ float wave_part[4];
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if ((int)blockIdx.x < active) {
@@ -104,6 +104,19 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
     if (threadIdx.x == 0) partials[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
 }
 
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, const uint8_t* __restrict__ group_of_8, long long n8,
+                                                    int active, float* __restrict__ partials) {
+    sumsq_body(g, group_of_8, n8, active, partials);
+}
+
+// Gated forms (gradient accumulation: one captured graph serves every micro-step of an update window).  Every thread of the grid reads
+// the same gate word first and the whole launch returns when it is 0: the partial sums, or every field of the state, keep their bits.
+__global__ __launch_bounds__(256) void sumsq_gated_kernel(const float* __restrict__ g, const uint8_t* __restrict__ group_of_8, long long n8,
+                                                          int active, float* __restrict__ partials, const int32_t* __restrict__ gate) {
+    if (*gate == 0) return;
+    sumsq_body(g, group_of_8, n8, active, partials);
+}
+
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -111,7 +124,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 }
 
 // One workgroup: all partials in double -> norm, clip coefficient, skip flag (vr_clip_state).
-__global__ __launch_bounds__(256) void clip_finish_kernel(const float* __restrict__ partials, int n, vr_clip_state* __restrict__ st) {
+__device__ __forceinline__ void clip_finish_body(const float* __restrict__ partials, int n, vr_clip_state* __restrict__ st) {
     __shared__ double wave_part[4];
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) s += (double)partials[i];
@@ -127,6 +140,16 @@ __global__ __launch_bounds__(256) void clip_finish_kernel(const float* __restric
         st->skip = bad ? 1 : 0;
         if (bad) st->skipped += 1;
     }
+}
+
+__global__ __launch_bounds__(256) void clip_finish_kernel(const float* __restrict__ partials, int n, vr_clip_state* __restrict__ st) {
+    clip_finish_body(partials, n, st);
+}
+
+__global__ __launch_bounds__(256) void clip_finish_gated_kernel(const float* __restrict__ partials, int n, vr_clip_state* __restrict__ st,
+                                                                const int32_t* __restrict__ gate) {
+    if (*gate == 0) return;
+    clip_finish_body(partials, n, st);
 }
 
 }  // namespace
@@ -182,24 +205,47 @@ extern "C" int vr_adamw_flat_dev_capped(float* p, const float* g, float* m, floa
 }
 
 // ---- gradient-norm clipping on the device (vr_clip_state) ----------------------------------------------------------------------
-extern "C" int vr_grad_sumsq(const float* g, const uint8_t* group_of_8, int64_t n, float* partials, int32_t n_partials,
-                             int32_t max_blocks, vr_stream_t stream) {
-    if (!g || !group_of_8 || !partials || n <= 0 || n_partials <= 0 || max_blocks < 0) return VR_EINVAL;
-    if (n % 8 || ((uintptr_t)g & 15)) return VR_EALIGN;
+static int sumsq_launch(const float* g, const uint8_t* group_of_8, int64_t n, float* partials, int32_t n_partials, int32_t max_blocks,
+                        const int32_t* gate, bool gated, vr_stream_t stream) {
+    if (!g || !group_of_8 || !partials || n <= 0 || n_partials <= 0 || max_blocks < 0 || (gated && !gate)) return VR_EINVAL;
+    if (n % 8 || ((uintptr_t)g & 15) || (gated && ((uintptr_t)gate & 3))) return VR_EALIGN;
     const long long n8 = n / 8;
     long long active = (n8 + 255) / 256;                           // workgroups that have work: the rest write 0
     if (active > n_partials) active = n_partials;
     if (max_blocks > 0 && active > max_blocks) active = max_blocks;
-    hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)n_partials), dim3(256), 0, (hipStream_t)stream, g, group_of_8, n8, (int)active,
-                       partials);
+    if (gated)
+        hipLaunchKernelGGL(sumsq_gated_kernel, dim3((unsigned)n_partials), dim3(256), 0, (hipStream_t)stream, g, group_of_8, n8, (int)active,
+                           partials, gate);
+    else
+        hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)n_partials), dim3(256), 0, (hipStream_t)stream, g, group_of_8, n8, (int)active,
+                           partials);
     VR_CHECK_LAUNCH();
     return VR_OK;
+}
+
+extern "C" int vr_grad_sumsq(const float* g, const uint8_t* group_of_8, int64_t n, float* partials, int32_t n_partials,
+                             int32_t max_blocks, vr_stream_t stream) {
+    return sumsq_launch(g, group_of_8, n, partials, n_partials, max_blocks, nullptr, false, stream);
+}
+
+extern "C" int vr_grad_sumsq_gated(const float* g, const uint8_t* group_of_8, int64_t n, float* partials, int32_t n_partials,
+                                   int32_t max_blocks, const int32_t* gate, vr_stream_t stream) {
+    return sumsq_launch(g, group_of_8, n, partials, n_partials, max_blocks, gate, true, stream);
 }
 
 extern "C" int vr_clip_finish(const float* partials, int32_t n_partials, vr_clip_state* state, vr_stream_t stream) {
     if (!partials || !state || n_partials <= 0) return VR_EINVAL;
     if ((uintptr_t)state & 3) return VR_EALIGN;
     hipLaunchKernelGGL(clip_finish_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)n_partials, state);
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
+
+extern "C" int vr_clip_finish_gated(const float* partials, int32_t n_partials, vr_clip_state* state, const int32_t* gate,
+                                    vr_stream_t stream) {
+    if (!partials || !state || !gate || n_partials <= 0) return VR_EINVAL;
+    if (((uintptr_t)state & 3) || ((uintptr_t)gate & 3)) return VR_EALIGN;
+    hipLaunchKernelGGL(clip_finish_gated_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (int)n_partials, state, gate);
     VR_CHECK_LAUNCH();
     return VR_OK;
 }

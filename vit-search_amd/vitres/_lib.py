@@ -68,6 +68,8 @@ SYMBOLS = {
     "vr_adamw_flat_dev_capped": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p],
     "vr_grad_sumsq": [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p],
     "vr_clip_finish": [c_void_p, c_int32, c_void_p, c_void_p],
+    "vr_grad_sumsq_gated": [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p],
+    "vr_clip_finish_gated": [c_void_p, c_int32, c_void_p, c_void_p, c_void_p],
     "vr_adamw_flat_clip": [c_void_p] * 6 + [c_float, c_void_p, c_void_p, c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p],
     "vr_cast_transpose_batch": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
     "vr_ln_fwd": [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_float, c_int32, c_void_p],
@@ -99,7 +101,9 @@ SYMBOLS = {
     "vr_sr_resid_bwd": [c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p],
     "vr_mask_rows": [c_void_p, c_void_p] + [c_int32] * 3 + [c_void_p],
     "vr_zero_ranges": [c_void_p, ctypes.POINTER(ZeroRanges), c_void_p],
+    "vr_zero_ranges_gated": [c_void_p, ctypes.POINTER(ZeroRanges), c_void_p, c_void_p],
     "vr_relayout": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p],
+    "vr_relayout_add": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p],
     "vr_im2col3x3": [c_void_p, c_void_p] + [c_int32] * 8 + [c_void_p],
     "vr_col2im3x3": [c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p],
     "vr_bn_stats": [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p],

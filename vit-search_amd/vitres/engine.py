@@ -214,8 +214,13 @@ class KnowledgeDistillationLoss(torch.nn.Module):
 
 def train_step(model, criterion, optimizer, samples, targets, patch_targets=None, patch_output_type=None, epoch=0,
                train_iter=0, arch_sample=None, grad_sync=None, loss_scaler=None, max_norm=None, average_grads=True,
-               teacher_output=None, kd_criterion=None, alpha=0.5):
-    """One optimisation step; returns the loss tensor (on device, not synchronised).  average_grads=False leaves the
+               teacher_output=None, kd_criterion=None, alpha=0.5, accum_steps=1, micro_step=0):
+    """One optimisation step -- or, with accum_steps = k > 1, micro-step `micro_step` (0..k-1) of an update window: micro-step 0 clears
+    the gradients, every micro-step adds its own, only micro-step k-1 exchanges, clips and steps the optimizer, on the MEAN over the
+    window (a vitres.optim.FlatAdamW divides by its accum_steps attribute, which is set here; for any other optimizer the loss is
+    divided by k before backward).  train_iter is the index of the optimizer UPDATE: all micro-steps of a window share the
+    'single' / 'hybrid' seed, as all ranks of one reference iteration do.
+    Returns this micro-batch's own (undivided) loss tensor (on device, not synchronised).  average_grads=False leaves the
     all-reduced SUM in the arena (optimizer applies 1/world: vitres.optim.FlatAdamW.grad_scale).  teacher_output +
     kd_criterion: knowledge distillation, loss = (1 - alpha) * criterion(cls) + alpha * kd(dst, teacher) (engine.py:135-148;
     a one-token model distils through its class logits, as the reference's `output_dst = outputs`).
@@ -223,6 +228,8 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
     clips on the device inside its own step (optimizer.max_norm is set to it: vr_grad_sumsq -> vr_clip_finish ->
     vr_adamw_flat_clip; optimizer.grad_norm() holds the norm afterwards); any other optimizer gets
     torch.nn.utils.clip_grad_norm_.  Either way after the all-reduce, so every rank clips the same averaged gradients."""
+    accum_steps = _check_accum(accum_steps, micro_step)
+    last = micro_step == accum_steps - 1
     rng = None
     if arch_sample is not None:                                   # engine.py:119-131
         rng = torch.random.get_rng_state()
@@ -247,7 +254,23 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
             raise ValueError()
     if rng is not None:
         torch.random.set_rng_state(rng)                           # engine.py:164-165
-    optimizer.zero_grad(set_to_none=True)
+    if micro_step == 0:
+        optimizer.zero_grad(set_to_none=True)
+    if accum_steps > 1:
+        flat_opt = hasattr(optimizer, "accum_steps")              # FlatAdamW averages inside its own pass
+        if flat_opt:
+            optimizer.accum_steps = accum_steps
+        own_loss, loss = loss, (loss if flat_opt else loss / accum_steps)
+        if not last:                                              # gradients only: autograd adds them to the window's sum
+            scaler = getattr(loss_scaler, '_scaler', None)
+            if loss_scaler is not None and scaler is None:
+                raise RuntimeError('gradient accumulation with a loss_scaler needs a NativeScaler-like object exposing `_scaler`')
+            (scaler.scale(loss) if scaler is not None else loss).backward()
+            if micro_step > 0 and hasattr(model, "rebind_grad_arena"):
+                model.rebind_grad_arena()
+            return own_loss.detach()
+    else:
+        own_loss = loss
     if loss_scaler is not None and (grad_sync is None or grad_sync.world == 1):
         loss_scaler(loss, optimizer, clip_grad=max_norm, parameters=model.parameters(), create_graph=False)
     elif loss_scaler is not None:
@@ -266,6 +289,8 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
         scaler.update()
     else:
         loss.backward()
+        if micro_step > 0 and hasattr(model, "rebind_grad_arena"):
+            model.rebind_grad_arena()                             # (autograd added this backward to the window's arena views)
         if grad_sync is not None:
             grad_sync.all_reduce_grads(average=average_grads)
         if max_norm and hasattr(optimizer, "clip_enabled"):       # FlatAdamW: one clipping path per optimizer type
@@ -273,7 +298,20 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
         elif max_norm:
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
         optimizer.step()
-    return loss.detach()
+    return own_loss.detach()
+
+
+def _check_accum(accum_steps, micro_step=0):
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+        raise ValueError("accum_steps must be an int >= 1, got %r" % (accum_steps,))
+    if not 0 <= micro_step < accum_steps:
+        raise ValueError("micro_step must lie in 0..accum_steps-1, got %r" % (micro_step,))
+    return accum_steps
+
+
+def _window(micro_step, accum_steps):
+    """Bookkeeping of an update window: (clear the arena?, apply the update?, position of the next micro-step)."""
+    return micro_step == 0, micro_step == accum_steps - 1, (micro_step + 1) % accum_steps
 
 
 # bounded run-ahead: the host needs ~3 ms for a 7.5 ms step, so left alone it queues replay after replay until the runtime's
@@ -289,10 +327,17 @@ class GraphedTrainStep:
     through static device buffers: the batch, the soft targets, and the int32 keep rows of every ChannelDrop, which
     are still sampled on the host with the reference's RNG protocol before each replay, and the DropPath scale vectors, drawn
     from the model's private CPU generator (model.drop_path_generator(): seeded from torch.initial_seed() + rank, saved and
-    restored with the checkpoint's RNG bundle).  The gradient exchange and the optimizer stay outside the graph."""
+    restored with the checkpoint's RNG bundle).  The gradient exchange and the optimizer stay outside the graph.
+
+    accum_steps = k > 1: gradient accumulation over k micro-batches per optimizer update with the SAME single graph.  Replay number
+    `micro_step` (0..k-1, the position of the NEXT replay; checkpoints belong where it is 0) of a window clears the arena only when it
+    is the first and runs the norm / clip / AdamW / EMA / shadow refresh only when it is the last: two int32 control words
+    {clear, apply} in device memory, rewritten before each replay over the plan buffer's pinned-staging route, gate those launches
+    (vr_zero_ranges_gated, vr_grad_sumsq_gated, vr_clip_finish_gated; AdamW reads the all-zero hyper-parameter block that
+    optimizer.prepare_step(apply=False) uploads).  Every gradient writer adds in place; the optimizer divides by k."""
 
     def __init__(self, model, criterion, samples, targets, patch_targets=None, patch_output_type=None, warmup=2,
-                 split_for_sync=False, optimizer=None, opt_overlap=1, opt_overlap_blocks=256):
+                 split_for_sync=False, optimizer=None, opt_overlap=1, opt_overlap_blocks=256, accum_steps=1):
         """split_for_sync: capture the backward as TWO graphs cut after the last stage (model.split_plan()), so that
         step_with_sync() can all-reduce the finished tail of the gradient arena (most of the parameters) while the rest
         of the backward -- most of the time -- is still running.
@@ -301,7 +346,11 @@ class GraphedTrainStep:
         the whole gradient norm is known: the early launches then are the SUMS OF SQUARES of those ranges (same stream, ranges and
         cap), and the remaining range's sum, the finish and ONE full-width AdamW follow the backward.  The replays follow
         optimizer.max_norm from value to value (float("inf"): measure only); switching it on or off after the capture makes
-        optimizer.prepare_step() raise."""
+        optimizer.prepare_step() raise.
+        accum_steps: micro-batches per optimizer update (class docstring).  With optimizer= the caller calls
+        optimizer.prepare_step(apply=(step.micro_step == accum_steps - 1)) before every replay."""
+        self.accum_steps = _check_accum(accum_steps)
+        self.micro_step = 0
         if hasattr(model, "_check_fp16_eval"):
             model._check_fp16_eval(True)          # (fp16 is an evaluation mode: nothing is captured or launched)
         self.model, self.criterion, self.pot = model, criterion, patch_output_type
@@ -314,6 +363,8 @@ class GraphedTrainStep:
         if self.optimizer is not None and split_for_sync:
             raise ValueError("optimizer-in-graph is for one rank; with a gradient exchange step the optimizer after step_with_sync")
         self.defer = None                    # (the deferred in-graph update is gone; bench.py still reads the attribute)
+        if self.accum_steps > 1 and self.optimizer is not None:
+            self.optimizer.accum_steps = self.accum_steps             # the update uses the window's mean
         # soft-target CE is the training loss of every shipped recipe (main.py:390-398): the whole step then runs without
         # autograd and without torch glue between the heads and the backward (model.loss_and_grad / vr_softce_train)
         from .losses import SoftTargetCrossEntropy
@@ -340,7 +391,17 @@ class GraphedTrainStep:
         self.keep_static = None                                   # (name kept: tests / tools look at it)
         self._plan_nk, self._stage, self._stage_i = 0, [], 0
         flat, nk = model.plan_host_buffer(plan)
-        if flat.size:
+        self._ctl_all = self._ctl = None
+        if self.accum_steps > 1:
+            # the control words {clear, apply} ride behind the plan in ONE device buffer: one staging copy per replay serves both
+            self._ctl_all = torch.ones(flat.size + 2, dtype=torch.int32, device=samples.device)
+            self._ctl = self._ctl_all[flat.size:]
+            self._plan_nk = nk
+            if flat.size:
+                self._ctl_all[:flat.size].copy_(torch.from_numpy(flat))
+                self.keep_static = self._ctl_all[:flat.size]
+            self._stage = [[torch.empty(flat.size + 2, dtype=torch.int32).pin_memory(), None] for _ in range(64)]
+        elif flat.size:
             self.keep_static = torch.from_numpy(flat).to(samples.device)
             self._plan_nk = nk
             self._stage = [[torch.empty(flat.size, dtype=torch.int32).pin_memory(), None] for _ in range(64)]
@@ -363,6 +424,10 @@ class GraphedTrainStep:
         from . import kernels as K
         K.ensure_workspaces(samples.device, roles=(0, 1))             # stream-K workspaces exist before anything is captured
         model._bwd_split = [c for c, _ in cuts] if cuts else None
+        gate_apply = None
+        if self._ctl is not None:
+            model._clear_gate = self._ctl[0:1]                     # the arena's clear inside the capture reads `clear` at run time
+            gate_apply = self._ctl[1:2]
         try:
             self._loss_buf = torch.zeros(1, dtype=torch.float32, device=samples.device)
             opt_cut = None
@@ -403,7 +468,7 @@ class GraphedTrainStep:
                             if clip:                                   # (each range fills its own slice of the partial sums)
                                 piece = self.optimizer.reserve_norm_slice(lo, hi)
                                 early = lambda lo=lo, hi=hi, piece=piece, cap=opt_overlap_blocks if Fn.OVERLAP else 0: \
-                                    self.optimizer.norm_range_device(lo, hi, piece, max_blocks=cap)       # noqa: E731
+                                    self.optimizer.norm_range_device(lo, hi, piece, max_blocks=cap, gate=gate_apply)  # noqa: E731
                             else:
                                 early = lambda lo=lo, hi=hi, cap=opt_overlap_blocks if Fn.OVERLAP else 0: \
                                     self.optimizer.step_device(lo, hi, max_blocks=cap)                    # noqa: E731
@@ -418,8 +483,8 @@ class GraphedTrainStep:
                         hi = n_arena
                     if clip:
                         # the last backward part joined the side stream: every early sum is complete in stream order
-                        self.optimizer.norm_range_device(0, hi, self.optimizer.reserve_norm_slice(0, hi))
-                        self.optimizer.clip_finish_device()
+                        self.optimizer.norm_range_device(0, hi, self.optimizer.reserve_norm_slice(0, hi), gate=gate_apply)
+                        self.optimizer.clip_finish_device(gate=gate_apply)
                         self.optimizer.step_device(0, n_arena, clip=True)
                     else:
                         self.optimizer.step_device(0, hi)
@@ -431,6 +496,8 @@ class GraphedTrainStep:
         finally:
             model._bwd_split = None
             model._bwd_join_parts = True
+            if self._ctl is not None:
+                model._clear_gate = None
         if self.more_graphs:
             self.graph_b = self.more_graphs[0]
             end = model._arena["gcur"].numel()
@@ -484,15 +551,23 @@ class GraphedTrainStep:
         plan = self.model.sample_plan(samples.shape[0])
         if rng is not None:
             torch.random.set_rng_state(rng)
-        if self.keep_static is not None:
-            flat, _ = self.model.plan_host_buffer(plan)
+        first, last, following = _window(self.micro_step, self.accum_steps)
+        if self.keep_static is not None or self._ctl_all is not None:
             slot = self._stage[self._stage_i % len(self._stage)]
             self._stage_i += 1
             if slot[1] is not None:
                 slot[1].synchronize()                             # the host runs ahead of the device: the block's last copy is done?
-            slot[0].numpy()[:] = flat
+            host = slot[0].numpy()
+            n_plan = 0
+            if self.keep_static is not None:
+                flat, _ = self.model.plan_host_buffer(plan)
+                n_plan = flat.size
+                host[:n_plan] = flat
+            if self._ctl_all is not None:                         # {clear, apply} of this replay
+                host[n_plan], host[n_plan + 1] = int(first), int(last)
             from . import kernels as K
-            K.copy_i32_from_pinned(slot[0], self.keep_static.view(-1))      # (a kernel reading pinned memory, not a memcpy)
+            # (a kernel reading pinned memory, not a memcpy)
+            K.copy_i32_from_pinned(slot[0], self._ctl_all if self._ctl_all is not None else self.keep_static.view(-1))
             slot[1] = torch.cuda.Event()
             slot[1].record()
         if self.col_static is not None:
@@ -508,12 +583,13 @@ class GraphedTrainStep:
         self.graph.replay()
         self.model._stem_fold = None                               # (stem.drop_fold: the replay moved BatchNorm's running statistics)
         for k, g in enumerate(self.more_graphs):
-            if self._sync is not None:                            # the arena range of the part just replayed is final: exchange it now
+            if self._sync is not None and last:                   # the arena range of the part just replayed is final: exchange it now
                 self._works.append(self._sync.all_reduce_range(*self.ranges[k]))
             g.replay()
         e_done = torch.cuda.Event()
         e_done.record()
         self._inflight.append(e_done)
+        self.micro_step = following
         return self.loss
 
     def finish_update(self):
@@ -526,12 +602,17 @@ class GraphedTrainStep:
     def step_with_sync(self, grad_sync, samples, targets, patch_targets=None, average=True, **kw):
         """Replay + data-parallel gradient exchange: with split_for_sync the all-reduce of the last stage's gradients
         overlaps the second backward graph; the remainder follows it.  Gradients are averaged on return (average=False:
-        summed -- for an optimizer that applies 1/world itself)."""
+        summed -- for an optimizer that applies 1/world itself).  accum_steps > 1: only the final micro-step of a window exchanges
+        (the window's summed gradients; the optimizer's accum_steps divides); the others issue no collective at all."""
+        _, last, _ = _window(self.micro_step, self.accum_steps)
         self._sync, self._works = grad_sync, []
         try:
             loss = self(samples, targets, patch_targets, **kw)
         finally:
             self._sync = None
+        if not last:
+            self._works = ()
+            return loss
         ev = None
         if getattr(self, "exposed", None) is not None and grad_sync.world > 1:
             ev = torch.cuda.Event(enable_timing=True)
@@ -551,7 +632,11 @@ class GraphedTrainStep:
 
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler=None, max_norm=0,
                     model_ema=None, mixup_fn=None, print_freq=100, teacher_model=None, hard_distill=True, alpha=0.5,
-                    logger=None, arch_sample=False, patch_mixup_fn=None, grad_sync=None, sync_every=1):
+                    logger=None, arch_sample=False, patch_mixup_fn=None, grad_sync=None, sync_every=1, accum_steps=1):
+    """accum_steps = k > 1: every k consecutive batches of the loader form one optimizer update (train_step's accum_steps /
+    micro_step); the iteration index of the seed rule, the EMA update and the learning-rate meter follow the UPDATES, the loss
+    meter every micro-batch.  A trailing incomplete window is dropped (the reference's loader is drop_last)."""
+    _check_accum(accum_steps)
     kd_criterion = None
     if teacher_model is not None:                                 # engine.py:91-95: any module mapping images to logits
         kd_criterion = KnowledgeDistillationLoss(hard_distill=hard_distill)
@@ -563,7 +648,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     arch_sample = arch_sample or None
     pending = []
     t0 = time.time()
-    for train_iter, (samples, targets) in enumerate(data_loader):
+    for step_i, (samples, targets) in enumerate(_full_windows(data_loader, accum_steps, print_out)):
+        train_iter, micro_step = divmod(step_i, accum_steps)      # train_iter: the optimizer update's index
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
         patch_targets, patch_output_type = None, None
@@ -580,9 +666,10 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
             grad_sync.broadcast_buffers()                         # DDP broadcast_buffers=True (main.py:367): per forward
         loss = train_step(model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, epoch,
                           train_iter, arch_sample, grad_sync, loss_scaler, max_norm, teacher_output=teacher_output,
-                          kd_criterion=kd_criterion, alpha=alpha)
+                          kd_criterion=kd_criterion, alpha=alpha, accum_steps=accum_steps, micro_step=micro_step)
         pending.append(loss)
-        if model_ema is not None:
+        final = micro_step == accum_steps - 1
+        if model_ema is not None and final:
             model_ema.update(model)
         if len(pending) >= sync_every:
             for v in torch.stack(pending).tolist():               # device -> host sync (reference: every iteration)
@@ -591,6 +678,8 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
                     sys.exit(1)
                 meters['loss'].update(v)
             pending = []
+        if not final:
+            continue
         meters['lr'].update(optimizer.param_groups[0]['lr'])
         if print_freq and train_iter % print_freq == 0:
             print_out('Epoch: [{}] [{}] loss: {:.4f} time: {:.1f}s'.format(epoch, train_iter, meters['loss'].global_avg,
@@ -604,6 +693,21 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         m.synchronize_between_processes()
     print_out('Averaged stats: ' + '  '.join('{}: {:.6f}'.format(k, m.global_avg) for k, m in meters.items()))
     return {k: m.global_avg for k, m in meters.items()}
+
+
+def _full_windows(data_loader, k, print_out=print):
+    """The loader's batches, minus a trailing window of fewer than k (k = 1: the loader itself)."""
+    if k == 1:
+        yield from data_loader
+        return
+    window = []
+    for batch in data_loader:
+        window.append(batch)
+        if len(window) == k:
+            yield from window
+            window = []
+    if window:
+        print_out('Dropped a trailing window of {} micro-batch(es): accum_steps is {}'.format(len(window), k))
 
 
 def accuracy(output, target, topk=(1,)):

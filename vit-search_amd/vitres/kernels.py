@@ -392,16 +392,23 @@ def _gemm_work(a, out, M, N, K, a_trans, rows_in, keep_k, keep_n, k_period, n_pe
     return flops, float((rows_in * kk).sum() * esz + float(kk.max()) * float(kn.max()) * esz + out_bytes)
 
 
-def zero_ranges(buf, ranges):
-    """buf[lo:hi] = 0 for every (lo, hi) of `ranges` (fp32 buffer; one launch per 24 ranges) -- vr_zero_ranges."""
+def zero_ranges(buf, ranges, gate=None):
+    """buf[lo:hi] = 0 for every (lo, hi) of `ranges` (fp32 buffer; one launch per 24 ranges) -- vr_zero_ranges.
+    gate: a device int32 tensor whose first element decides at run time whether the launch does anything (0: the buffer keeps its
+    contents) -- vr_zero_ranges_gated, for a captured graph that serves every micro-step of a gradient-accumulation window."""
     ranges = [(int(lo), int(hi)) for lo, hi in ranges if hi > lo]
+    if gate is not None:
+        assert gate.dtype == torch.int32 and gate.device == buf.device and gate.numel() >= 1
     for i in range(0, len(ranges), _lib.MAX_ZERO_RANGES):
         chunk = ranges[i:i + _lib.MAX_ZERO_RANGES]
         zr = _lib.ZeroRanges()
         zr.n = len(chunk)
         for j, (lo, hi) in enumerate(chunk):
             zr.lo[j], zr.count[j] = lo, hi - lo
-        _lib.check(_lib.lib().vr_zero_ranges(_p(buf), ctypes.byref(zr), _stream()), "vr_zero_ranges")
+        if gate is not None:
+            _lib.check(_lib.lib().vr_zero_ranges_gated(_p(buf), ctypes.byref(zr), _p(gate), _stream()), "vr_zero_ranges_gated")
+        else:
+            _lib.check(_lib.lib().vr_zero_ranges(_p(buf), ctypes.byref(zr), _stream()), "vr_zero_ranges")
     return buf
 
 
@@ -425,6 +432,22 @@ def relayout(src, dst, A, B, C, dst_ld=None, src_ld=None):
     src_ld = B * C if src_ld is None else src_ld
     _lib.check(_lib.lib().vr_relayout(_p(src), _p(dst), A, B, C, src_ld, dst_ld, _dt(src), _dt(dst), _stream()), "vr_relayout")
     return dst
+
+
+def relayout_add(src, dst, A, B, C, dst_ld=None, src_ld=None):
+    """dst[a, c, b] += src[a, b, c], fp32 both sides, relayout()'s index map -- vr_relayout_add.  A = B = 1: dst += src (flat)."""
+    if src.dtype != torch.float32 or dst.dtype != torch.float32:
+        raise ValueError("relayout_add: fp32 tensors only")
+    dst_ld = B * C if dst_ld is None else dst_ld
+    src_ld = B * C if src_ld is None else src_ld
+    _lib.check(_lib.lib().vr_relayout_add(_p(src), _p(dst), A, B, C, src_ld, dst_ld, _stream()), "vr_relayout_add")
+    return dst
+
+
+def put_grad(src, dst, A, B, C, src_ld=None, add=False):
+    """A gradient that was formed in a temporary goes to its place in the arena: stored (relayout) when the arena was cleared for
+    this backward, added (relayout_add) when it holds the sum of earlier micro-steps."""
+    return relayout_add(src, dst, A, B, C, src_ld=src_ld) if add else relayout(src, dst, A, B, C, src_ld=src_ld)
 
 
 def copy_i32_from_pinned(host, dst):

@@ -417,11 +417,25 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         if cached is None or cached[0] != buf.numel():
             cached = a["zero_ranges"] = (buf.numel(), [(0, buf.numel())], 0)
         if buf.is_cuda:
-            K.zero_ranges(buf, cached[1])
+            # _clear_gate (engine.GraphedTrainStep(accum_steps > 1) sets it around its capture): the clear is decided per replay
+            K.zero_ranges(buf, cached[1], gate=getattr(self, "_clear_gate", None))
         else:
             for lo, hi in cached[1]:
                 buf[lo:hi].zero_()
         return cached[2]
+
+    def rebind_grad_arena(self):
+        """After autograd ADDED a further backward to `.grad` tensors that are views of the flat gradient arena (that backward
+        itself ran into a scratch arena: _run_backward), the flat arena is the current one again -- what FlatAdamW.step() and
+        GradSync read.  Returns False when the gradients are not views of the arena (nothing is changed then)."""
+        a = self._arena
+        if a is None or a.get("gflat") is None:
+            return False
+        p0 = a["params"][0]
+        if p0.grad is None or p0.grad.data_ptr() != a["gflat"].data_ptr() + 4 * a["offsets"][0][0]:
+            return False
+        a["gcur"] = a["gflat"]
+        return True
 
     def _gview(self, p):
         a = self._arena
@@ -714,14 +728,16 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             out = tuple(o.index_select(0, inv_idx) for o in out) if isinstance(out, tuple) else out.index_select(0, inv_idx)
         return out
 
-    def loss_and_grad(self, x, targets, patch_targets=None, patch_output_type=None, plan=None, loss_out=None):
+    def loss_and_grad(self, x, targets, patch_targets=None, patch_output_type=None, plan=None, loss_out=None, accumulate=False):
         """Forward + soft-target cross entropy of the training loop (engine.py:135-157 with timm's SoftTargetCrossEntropy:
         CE(cls, targets) [+ CE(patch, patch_targets) for 'seq' / CE(patch_mean, targets) for 'avg'; two-token models: CE of the
         class logits only, as the reference's no-teacher branch] + backward, WITHOUT autograd: the logits never leave the internal
         sample order, vr_softce_train scores them against the caller-ordered targets, accumulates the mean loss and writes the
         logit gradients in the layout the head's backward GEMMs read.  Same gradients as `loss.backward()` on forward()'s
         outputs; they land in the flat arena and are exposed as `p.grad`.  Requires zero_grad(set_to_none=True) since the last
-        backward.  Returns the loss as a 0-d device tensor (loss_out: a preallocated fp32 [1] buffer, e.g. under hipGraph capture)."""
+        backward -- unless accumulate=True: gradients a previous loss_and_grad left in the arena are kept and this call's are ADDED to
+        them in place (gradient accumulation over micro-batches: no clear is issued, no second arena, no `acc += g` pass).
+        Returns the loss as a 0-d device tensor (loss_out: a preallocated fp32 [1] buffer, e.g. under hipGraph capture)."""
         self._check_fp16_eval(True)
         if _REQUIRE_CUDA and not x.is_cuda:
             raise RuntimeError('vitres runs on MI355X through libvitres_hip.so only; got a %s tensor' % x.device)
@@ -730,8 +746,15 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         if patch_output_type not in (None, 'seq', 'avg'):
             raise ValueError()
         a = self._ensure_arena(x.device)
-        if any(p_.grad is not None for p_ in a["params"]):
+        have = any(p_.grad is not None for p_ in a["params"])
+        if have and not accumulate:
             raise RuntimeError('loss_and_grad needs fresh gradients: zero_grad(set_to_none=True) first')
+        if have:
+            p0, g0 = a["params"][0], a.get("gflat")
+            if g0 is None or a.get("gcur") is not g0 or p0.grad is None or \
+                    p0.grad.data_ptr() != g0.data_ptr() + 4 * a["offsets"][0][0]:
+                raise RuntimeError('loss_and_grad(accumulate=True) adds to gradients a previous loss_and_grad left in the flat arena; '
+                                   'these are not views of it')
         use_patch = bool(self.patch_output and patch_targets is not None or (self.patch_output and patch_output_type == 'avg'))
         with_patch = (2 if patch_output_type == 'avg' else 1) if (self.patch_output and use_patch) else 0
         if self.num_tokens == 2:
@@ -758,7 +781,11 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                 dpat = K.softce_train(pat, patch_targets.float(), smap, pat.shape[1], loss, dt)
             elif with_patch == 2:
                 dpat = K.softce_train(pat, targets.float(), smap, 1, loss, dt)
-            self._run_backward(tape, plan, dcls, dpat, ready=True)
+            self._acc_keep = have                      # (accumulate: _run_backward keeps the arena and adds)
+            try:
+                self._run_backward(tape, plan, dcls, dpat, ready=True)
+            finally:
+                self._acc_keep = False
             for p_ in a["params"]:
                 if p_.requires_grad:
                     p_.grad = self._gview(p_)
@@ -951,7 +978,10 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             a["gflat"] = torch.zeros_like(a["flat"])
         # grads already live in the arena (no zero_grad since the last backward): use a scratch arena so that
         # autograd's accumulation adds a separate buffer
-        a["gcur"] = a["gflat"] if fresh else torch.zeros_like(a["flat"])
+        keep = bool(getattr(self, "_acc_keep", False)) and not fresh      # loss_and_grad(accumulate=True): add in place
+        a["gcur"] = a["gflat"] if (fresh or keep) else torch.zeros_like(a["flat"])
+        # the arena may hold earlier micro-steps' sums: the writers that go through a temporary add instead of storing
+        self._acc_add = keep or getattr(self, "_clear_gate", None) is not None
         if fresh and not a.pop("gzeroed", False):      # (the forward may have zeroed it on the side stream already)
             self._zero_grad_arena(a["gcur"], plan.batch)
         a["gzeroed"] = False
@@ -1088,9 +1118,13 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                 ztmp = K.zero_(torch.empty(co * 9 * ci + (nt + blk.num_patches) * co, dtype=torch.float32, device=dev))   # one fill
                 wtmp = ztmp[:co * 9 * ci].view(co, 9 * ci)
                 ptmp = ztmp[co * 9 * ci:].view(nt + blk.num_patches, co)
-                def finish(blk=blk, wtmp=wtmp, ptmp=ptmp, co=co, ci=ci, nt=nt):     # runs on the stream of the weight gradients
-                    K.relayout(wtmp, gv(blk.patch_reduce.weight), co, 9, ci)         # [co, (kh, kw), ci] -> [co, ci, kh, kw]
-                    gv(blk.pos_embed).copy_(ptmp[nt:].unsqueeze(0))
+                def finish(blk=blk, wtmp=wtmp, ptmp=ptmp, co=co, ci=ci, nt=nt, add=getattr(self, "_acc_add", False)):
+                    # (runs on the stream of the weight gradients)     [co, (kh, kw), ci] -> [co, ci, kh, kw]
+                    K.put_grad(wtmp, gv(blk.patch_reduce.weight), co, 9, ci, add=add)
+                    if add:
+                        K.relayout_add(ptmp[nt:], gv(blk.pos_embed), 1, 1, blk.num_patches * co)
+                    else:
+                        gv(blk.pos_embed).copy_(ptmp[nt:].unsqueeze(0))
                 grads = {"nw": gv(blk.norm.weight), "nb": gv(blk.norm.bias), "token.w": gv(blk.token_transform.weight),
                          "token.b": gv(blk.token_transform.bias), "reduce.b": gv(blk.patch_reduce.bias),
                          "reduce.w": wtmp, "pos_sum": ptmp, "finish": finish}
@@ -1109,10 +1143,11 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                                                                                         device=dev))
                     grads = {"proj.w": wt, "proj.b": gv(self.patch_embed.proj.bias), "pos": gv(self.pos_embed)}
 
-                    def tail(wgrad=True, pos=True, g=g, sv=sv, ep=ep, grads=grads, ecfg=ecfg, ekeep=ekeep, gt=gt, wt=wt, w=w, k=k, ld=ld):
+                    def tail(wgrad=True, pos=True, g=g, sv=sv, ep=ep, grads=grads, ecfg=ecfg, ekeep=ekeep, gt=gt, wt=wt, w=w, k=k, ld=ld,
+                             add=getattr(self, "_acc_add", False)):
                         Fn.embed0_bwd(g, sv, ep, grads, ecfg, ekeep, gt=gt, wgrad=wgrad, pos=pos)
                         if wgrad and ld != k:
-                            K.relayout(wt, gv(w), w.shape[0], 1, k, src_ld=ld)   # drop the pad columns
+                            K.put_grad(wt, gv(w), w.shape[0], 1, k, src_ld=ld, add=add)   # drop the pad columns
                         if pos:
                             gv(self.tokens).copy_(gv(self.pos_embed)[:, 0:self.num_tokens, :])
                     if Fn._overlap(g):

@@ -36,6 +36,12 @@ class _ClipState(ctypes.Structure):            # vr_clip_state (include/vitres_h
                 ("skip", ctypes.c_int32), ("skipped", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
+def _check_accum_steps(v):
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError("accum_steps must be an int >= 1, got %r" % (v,))
+    return v
+
+
 def _check_max_norm(v):
     if v is None:
         return None
@@ -46,7 +52,8 @@ def _check_max_norm(v):
 
 
 class FlatAdamW(torch.optim.Optimizer):
-    def __init__(self, model, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None, max_norm=None):
+    def __init__(self, model, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, ema_decay=None, max_norm=None,
+                 accum_steps=1):
         """params: iterable of parameters or of param-group dicts (as torch.optim.AdamW); every parameter must belong to
         `model`, whose arena they live in.  ema_decay: keep an exponential moving average of the parameters
         (`ema_state_dict()` returns it under the model's state_dict keys).
@@ -57,7 +64,11 @@ class FlatAdamW(torch.optim.Optimizer):
         norm is inf or NaN changes NOTHING on the device -- parameters, moments, EMA and bf16 shadow keep their values
         (skipped_steps() counts them) -- where torch's formula would turn every parameter into NaN.  The host step count still
         advances on such a step: the host runs ahead of the device and cannot know.  Against torch.cuda.amp.GradScaler, which does
-        not count a skipped step, only the bias corrections of the later steps differ (they are one step further along)."""
+        not count a skipped step, only the bias corrections of the later steps differ (they are one step further along).
+        accum_steps (an int >= 1, a plain attribute like grad_scale): the arena holds the SUM of the gradients of that many
+        micro-batches (loss_and_grad(accumulate=True), engine.GraphedTrainStep(accum_steps=k)); the update uses their mean: every
+        gradient is multiplied by grad_scale / accum_steps, so grad_norm(), clipping and the skip rule see the averaged gradient.
+        The step count and the bias corrections count optimizer updates, not micro-batches."""
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         if len(self.param_groups) > MAX_GROUPS:
             raise ValueError("at most %d parameter groups" % MAX_GROUPS)
@@ -67,12 +78,17 @@ class FlatAdamW(torch.optim.Optimizer):
         self._arena_id = None
         self.grad_scale = 1.0              # e.g. 1/world when the all-reduce leaves a SUM in the gradient arena
         self.max_norm = _check_max_norm(max_norm)
+        self.accum_steps = _check_accum_steps(accum_steps)
         self._clip = None                  # device state of the clipping launches: allocated by the first step that clips
         self._graph_clip = None            # engine.GraphedTrainStep: whether its captured graph holds the clipping launches
 
     # ---- gradient-norm clipping ---------------------------------------------------------------------------------
     def clip_enabled(self):
         return bool(_check_max_norm(self.max_norm))
+
+    def _grad_factor(self):
+        """What every gradient element is multiplied by: grad_scale (the caller's 1/world) / accum_steps (mean over the window)."""
+        return float(self.grad_scale) / _check_accum_steps(self.accum_steps)
 
     def _clip_bind(self, dev):
         c = self._clip
@@ -88,7 +104,7 @@ class FlatAdamW(torch.optim.Optimizer):
     def _clip_upload(self, dev, pinned=False):
         """max_norm and grad_scale -> the input half of the device's vr_clip_state (the output half is the device's own)."""
         c = self._clip_bind(dev)
-        host = torch.tensor([_check_max_norm(self.max_norm), float(self.grad_scale)], dtype=torch.float32)
+        host = torch.tensor([_check_max_norm(self.max_norm), self._grad_factor()], dtype=torch.float32)
         if pinned and dev.type == "cuda":
             host = host.pin_memory()       # (a fresh block per step, as for the hyper-parameters in prepare_step)
         c["state"][:2].copy_(host, non_blocking=pinned)
@@ -105,9 +121,10 @@ class FlatAdamW(torch.optim.Optimizer):
         return first, count
 
     @torch.no_grad()
-    def norm_range_device(self, lo, hi, piece, max_blocks=0):
+    def norm_range_device(self, lo, hi, piece, max_blocks=0, gate=None):
         """Sum of squares of the gradient arena range [lo, hi) (multiples of 8) into the slice `piece` = reserve_norm_slice(lo,
-        hi) of the partial sums: capturable.  max_blocks as for step_device."""
+        hi) of the partial sums: capturable.  max_blocks as for step_device.  gate: a device int32 word read at run time; 0 makes
+        the launch a no-op that leaves the slice untouched (vr_grad_sumsq_gated: non-final micro-steps of an accumulation window)."""
         a = self._bind()
         g = a.get("gcur")
         n = a["flat"].numel()
@@ -119,17 +136,27 @@ class FlatAdamW(torch.optim.Optimizer):
         first, count = piece
         if not (0 <= first and count > 0 and first + count <= c["partials"].numel()):
             raise ValueError("piece is not a slice of the partial-sum buffer")
+        if gate is not None:
+            _lib.check(_lib.lib().vr_grad_sumsq_gated(g.data_ptr() + 4 * lo, self._flat_state["gid"].data_ptr() + lo // 8, hi - lo,
+                                                      c["partials"].data_ptr() + 4 * first, count, int(max_blocks), _p(gate),
+                                                      _stream()), "vr_grad_sumsq_gated")
+            return
         _lib.check(_lib.lib().vr_grad_sumsq(g.data_ptr() + 4 * lo, self._flat_state["gid"].data_ptr() + lo // 8, hi - lo,
                                             c["partials"].data_ptr() + 4 * first, count, int(max_blocks), _stream()),
                    "vr_grad_sumsq")
 
     @torch.no_grad()
-    def clip_finish_device(self):
-        """Partial sums of every norm_range_device since the last call -> norm, clip coefficient and skip flag on the device."""
+    def clip_finish_device(self, gate=None):
+        """Partial sums of every norm_range_device since the last call -> norm, clip coefficient and skip flag on the device.
+        gate: as for norm_range_device; gate 0 leaves every field of the device state untouched (vr_clip_finish_gated)."""
         c = self._clip
         if c is None or c["used"] == 0:
             raise RuntimeError("clip_finish_device needs norm_range_device launches before it")
-        _lib.check(_lib.lib().vr_clip_finish(_p(c["partials"]), c["used"], _p(c["state"]), _stream()), "vr_clip_finish")
+        if gate is not None:
+            _lib.check(_lib.lib().vr_clip_finish_gated(_p(c["partials"]), c["used"], _p(c["state"]), _p(gate), _stream()),
+                       "vr_clip_finish_gated")
+        else:
+            _lib.check(_lib.lib().vr_clip_finish(_p(c["partials"]), c["used"], _p(c["state"]), _stream()), "vr_clip_finish")
         c["used"] = 0
 
     def grad_norm(self):
@@ -204,11 +231,14 @@ class FlatAdamW(torch.optim.Optimizer):
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
             arr[gi] = _Group(group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t,
-                             math.sqrt(1.0 - b2 ** t), self.grad_scale)
+                             math.sqrt(1.0 - b2 ** t), self._grad_factor())
         return arr
 
-    def prepare_step(self):
-        """Advance the step count and upload this step's per-group hyper-parameters (learning rates written by the scheduler,
+    def prepare_step(self, apply=True):
+        """apply=False (a non-final micro-step of an accumulation window: engine.GraphedTrainStep(accum_steps=k), k > 1): the step
+        count stays and an ALL-ZERO hyper-parameter block is uploaded -- the captured AdamW launches skip every group whose bias_c1
+        is 0, so the replay changes no parameter, moment, EMA or shadow element.  apply=True:
+        Advance the step count and upload this step's per-group hyper-parameters (learning rates written by the scheduler,
         bias corrections) to the device buffer step_device() launches read -- call once before every replay of a graph that
         contains step_device() launches (engine.GraphedTrainStep(optimizer=...)).  With max_norm set, max_norm and grad_scale
         are uploaded too; a graph holds the clipping launches or not from its capture on, so switching max_norm between on and
@@ -222,17 +252,18 @@ class FlatAdamW(torch.optim.Optimizer):
         dev = a["flat"].device
         if getattr(self, "_hp_dev", None) is None or self._hp_dev.device != dev:
             self._hp_dev = torch.zeros(MAX_GROUPS * 8, dtype=torch.float32, device=dev)
-        self._step += 1
-        self.model._stem_fold = None           # parameters change through raw pointers: no Tensor._version moves (stem.drop_fold)
-        arr = self._group_structs(self._step)
-        vals = [getattr(arr[gi], n) for gi in range(len(self.param_groups)) for n, _ in _Group._fields_]
         host = torch.zeros(MAX_GROUPS * 8, dtype=torch.float32)
-        host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
+        if apply:
+            self._step += 1
+            self.model._stem_fold = None       # parameters change through raw pointers: no Tensor._version moves (stem.drop_fold)
+            arr = self._group_structs(self._step)
+            vals = [getattr(arr[gi], n) for gi in range(len(self.param_groups)) for n, _ in _Group._fields_]
+            host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
         if dev.type == "cuda":
             host = host.pin_memory()       # a fresh pinned block per step: the host runs several replays ahead of the device, a
                                            # reused staging buffer would be overwritten before its copy has executed
         self._hp_dev.copy_(host, non_blocking=True)
-        if self.clip_enabled():
+        if apply and self.clip_enabled():
             self._clip_upload(dev, pinned=True)
 
     @torch.no_grad()

@@ -228,12 +228,13 @@ def embed_conv_bwd(model, gx, saved, p, cfg, keep, gv, gt=None):
         gt = K.scale_mask_cast(gx, None, keep, N, dt)
     # conv_proj
     ov = Fn._overlap(gx)
+    acc = bool(getattr(model, "_acc_add", False))    # gradient accumulation: the arena holds earlier micro-steps' sums
     wtmp = K.zero_(torch.empty((C, ldk), dtype=torch.float32, device=dev))
 
     def wgrad_proj():
         Fn.linear_wgrad(gt, colp, wtmp, B * P, C, ldk, C, ldk, a_map=(P, N, T), db=gv(pe.conv_proj.bias),
                         sched=1 if ov else 0)
-        K.relayout(wtmp, gv(pe.conv_proj.weight), C, ps * ps, m)          # [C, (kh, kw), m] -> [C, m, kh, kw]
+        K.put_grad(wtmp, gv(pe.conv_proj.weight), C, ps * ps, m, add=acc)   # [C, (kh, kw), m] -> [C, m, kh, kw]
         K.batchsum(gx, gv(model.pos_embed))
     # weight gradients run beside the data-gradient chain (functional.on_side); joined at the end of this function
     Fn.on_side(wgrad_proj, gt, wtmp) if ov else wgrad_proj()
@@ -241,19 +242,19 @@ def embed_conv_bwd(model, gx, saved, p, cfg, keep, gv, gt=None):
     K.gemm(gt, p["proj"].w_c, dcolp, M=B * P, N=ldk, K=C, lda=C, ldb=ldk, ldc=ldk, b_trans=True, a_map=(P, N, T))
     da3 = dcolp if pdirect else K.patch_fold(dcolp, B, g, g, ps, m)     # d(relu(bn3) + a1); pdirect: still in patch order
 
-    acc_in_place = True      # (every backward starts from a zeroed gradient arena: vit_sr_supernet._run_backward / _zero_grad_arena)
+    # a backward that starts from a zeroed gradient arena (vit_sr_supernet._run_backward / _zero_grad_arena) lets vr_bn_bwd sum straight
+    # into it; under accumulation the arena is not zero, and the kernel READS the sums it has just formed for dz: temporaries then
 
     def conv_bwd(da, z, bn, col, w, conv_mod, ld, need_dx, wt=None, res=None, da_patch=False, res_patch=False):
         gbw, gbb = gv(conv_mod.bn.weight), gv(conv_mod.bn.bias)
-        if da_patch:                            # (pdirect implies acc_in_place's fast path)
-            dz = K.bn_bwd_patch(da, z, bn[0], bn[1], bn[2], bn[3], gbb, gbw, tr, B, Hm, Wm, ps)
-        elif acc_in_place:                      # the gradient arena is zero here: vr_bn_bwd's sums land where they belong
-            dz = K.bn_bwd(da, z, bn[0], bn[1], bn[2], bn[3], gbb, gbw, tr)
-        else:
-            sg = K.zero_(torch.empty((2, m), dtype=torch.float32, device=dev))
+        sg = K.zero_(torch.empty((2, m), dtype=torch.float32, device=dev)) if acc else (gbb, gbw)
+        if da_patch:
+            dz = K.bn_bwd_patch(da, z, bn[0], bn[1], bn[2], bn[3], sg[0], sg[1], tr, B, Hm, Wm, ps)
+        else:                                   # (in place: the gradient arena is zero here, vr_bn_bwd's sums land where they belong)
             dz = K.bn_bwd(da, z, bn[0], bn[1], bn[2], bn[3], sg[0], sg[1], tr)
-            gbw.copy_(sg[1])
-            gbb.copy_(sg[0])
+        if acc:
+            K.relayout_add(sg[1], gbw, 1, 1, m)
+            K.relayout_add(sg[0], gbb, 1, 1, m)
         wg = K.zero_(torch.empty((m, ld), dtype=torch.float32, device=dev))
         cin = conv_mod.conv.weight.shape[1]
         direct_w = wt is not None and K.conv3x3_wgrad_supported(dz, cin, m)
@@ -268,7 +269,7 @@ def embed_conv_bwd(model, gx, saved, p, cfg, keep, gv, gt=None):
                 if isinstance(c_, tuple):       # conv1 ran straight from the image: its im2col matrix is built here
                     c_ = K.im2col3x3_image(c_[1], 2, ld, dt)
                 Fn.linear_wgrad(dz, c_, wg, R, m, ld, m, ld, sched=1 if ov else 0)
-            K.relayout(wg, gv(conv_mod.conv.weight), m, 9, cin, src_ld=ld)     # [m, (kh, kw), ci] -> [m, ci, kh, kw]
+            K.put_grad(wg, gv(conv_mod.conv.weight), m, 9, cin, src_ld=ld, add=acc)     # [m, (kh, kw), ci] -> [m, ci, kh, kw]
         Fn.on_side(wgrad, dz, wg) if ov else wgrad()
         if not need_dx:
             return None
