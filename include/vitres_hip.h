@@ -378,6 +378,28 @@ int vr_softce_train(const float* logits, const float* target, const int64_t* sam
                     float* loss_acc, void* dlogits, int32_t ld_grad, int32_t grad_dtype, int32_t R, int32_t K,
                     float gscale, float loss_scale, vr_stream_t stream);
 
+/*
+ * Evaluation metrics of one batch, accumulated on the device (engine.py:213-238: CrossEntropyLoss + timm accuracy(topk=(1, 5)) of the
+ * class logits and, for two-token models, of the distillation logits and of softmax(logits) + softmax(logits2)).  logits / logits2:
+ * fp32 [R, K] with row pitch ld >= K; labels: int64 [R].  Per row CE = logsumexp(x) - x[y] in fp32, summed in double;
+ * rank = #{k : v[k] > v[y]} + #{k < y : v[k] == v[y]}, top1 = rank < 1, top5 = rank < min(5, K): exact comparisons on the raw
+ * logits (top1 is argmax(...) == y, ties to the lowest index); the joint head ranks v = exp(x - lse) + exp(x2 - lse2) in fp32.
+ * A row whose label lies outside [0, K) or that holds a NaN logit is a miss everywhere and makes loss_sum NaN; it reads nothing out
+ * of range.  One workgroup per call, no floating-point atomics: equal inputs and equal state give equal bits.  Calls on one state
+ * are ordered by the stream.  16-byte loads when ld % 4 == 0 and both logit pointers are 16-byte aligned.
+ * VR_EINVAL: R <= 0, K <= 0, ld < K or a NULL logits / labels / state; VR_EALIGN: state or labels not 8-byte, logits not 4-byte aligned.
+ */
+typedef struct vr_eval_state {   /* device memory; the caller zeroes it once per evaluation */
+    double  loss_sum;            /* += mean over this call's R rows of CE(logits[r], labels[r]) */
+    int64_t calls, rows;         /* += 1, += R */
+    int64_t top1, top5;          /* hits of `logits` */
+    int64_t dst_top1, dst_top5;  /* hits of `logits2`            (untouched when logits2 == NULL) */
+    int64_t jnt_top1, jnt_top5;  /* hits of softmax(logits) + softmax(logits2) (likewise)         */
+    int64_t reserved;
+} vr_eval_state;
+int vr_eval_metrics(const float* logits, const float* logits2 /* nullable */, const int64_t* labels,
+                    int32_t R, int32_t K, int32_t ld, vr_eval_state* state, vr_stream_t stream);
+
 /* out[n] += sum_m in[map(m), n]  (bias gradients; atomics, caller zeroes out).  in: dtype [*, ld]. */
 int vr_colsum(const void* in, float* out, int32_t M, int32_t N, int32_t ld, int32_t dtype, vr_rowmap map, vr_stream_t stream);
 

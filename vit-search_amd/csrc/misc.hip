@@ -100,6 +100,131 @@ __global__ __launch_bounds__(256) void softce_kernel(const float* __restrict__ x
     }
 }
 
+// ---- evaluation metrics: hard-label cross entropy and top-1 / top-5 hits, wave per row, ONE workgroup per call -------------------
+// The rank of the label's value v[y] among the row, #{k : v[k] > v[y]} + #{k < y : v[k] == v[y]}, decides a hit (rank < 1, rank <
+// min(5, K)): exact comparisons on raw logits, so top-1 is argmax(...) == y with torch's first-index tie rule.  One workgroup: its
+// waves walk the rows in a fixed order and thread 0 folds their partial sums in wave order -- no floating-point atomics, equal inputs
+// give equal bits; the 2 MB of a 256 x 1000 two-head batch are nothing beside the forward that made them.
+struct EvalRow {
+    float lse;
+    bool nan;
+};
+
+// v(k) of a row for the loop bodies below: chunks of four from 16-byte loads where the chunk lies inside [0, K), scalars at the tail
+template <typename F> __device__ __forceinline__ void eval_row_each(const float* __restrict__ xr, int K, bool vec, int lane, F&& f) {
+    if (vec) {
+        const int k4 = K & ~3;
+        for (int k = lane * 4; k < k4; k += 256) {
+            const float4 v = *reinterpret_cast<const float4*>(xr + k);
+            f(k, v.x); f(k + 1, v.y); f(k + 2, v.z); f(k + 3, v.w);
+        }
+        if (lane < K - k4) f(k4 + lane, xr[k4 + lane]);
+    } else {
+        for (int k = lane; k < K; k += 64) f(k, xr[k]);
+    }
+}
+
+// the same walk over two rows of one pitch at once: f(k, a[k], b[k])
+template <typename F>
+__device__ __forceinline__ void eval_rows_each2(const float* __restrict__ ar, const float* __restrict__ br, int K, bool vec, int lane,
+                                                F&& f) {
+    if (vec) {
+        const int k4 = K & ~3;
+        for (int k = lane * 4; k < k4; k += 256) {
+            const float4 a = *reinterpret_cast<const float4*>(ar + k);
+            const float4 b = *reinterpret_cast<const float4*>(br + k);
+            f(k, a.x, b.x); f(k + 1, a.y, b.y); f(k + 2, a.z, b.z); f(k + 3, a.w, b.w);
+        }
+        if (lane < K - k4) f(k4 + lane, ar[k4 + lane], br[k4 + lane]);
+    } else {
+        for (int k = lane; k < K; k += 64) f(k, ar[k], br[k]);
+    }
+}
+
+__device__ __forceinline__ int wave_sum_i(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ EvalRow eval_row_lse(const float* __restrict__ xr, int K, bool vec, int lane) {
+    float mx = -INFINITY;
+    int bad = 0;
+    eval_row_each(xr, K, vec, lane, [&](int, float v) { mx = fmaxf(mx, v); bad |= (v != v); });
+    mx = wave_max(mx);
+    float se = 0.f;
+    eval_row_each(xr, K, vec, lane, [&](int, float v) { se += __expf(v - mx); });
+    se = wave_sum(se);
+    return EvalRow{mx + __logf(se), wave_sum_i(bad) != 0};
+}
+
+__device__ __forceinline__ float eval_joint(float a, float lse_a, float b, float lse_b) { return __expf(a - lse_a) + __expf(b - lse_b); }
+
+#define VR_EVAL_MAX_WAVES 16
+__global__ __launch_bounds__(64 * VR_EVAL_MAX_WAVES) void eval_metrics_kernel(const float* __restrict__ x, const float* __restrict__ x2,
+                                                                             const long long* __restrict__ labels, int R, int K, int ld,
+                                                                             int vec, vr_eval_state* __restrict__ state) {
+    __shared__ double s_loss[VR_EVAL_MAX_WAVES];
+    __shared__ int s_hits[VR_EVAL_MAX_WAVES][6];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = blockDim.x >> 6;
+    const int top = K < 5 ? K : 5;
+    double loss = 0.0;
+    int hits[6] = {0, 0, 0, 0, 0, 0};
+    for (int r = wave; r < R; r += waves) {
+        const float* xr = x + (long long)r * ld;
+        const float* yr = x2 ? x2 + (long long)r * ld : nullptr;
+        const long long label = labels[r];
+        const bool in_range = label >= 0 && label < K;
+        const int y = in_range ? (int)label : 0;                  // (a bad label reads column 0: nothing out of range)
+        const EvalRow a = eval_row_lse(xr, K, vec, lane);
+        const float xy = xr[y];
+        bool bad = !in_range || a.nan;
+        int c = 0;
+        eval_row_each(xr, K, vec, lane, [&](int k, float v) { c += (k != y) & ((v > xy) | ((k < y) & (v == xy))); });
+        c = wave_sum_i(c);
+        int c2 = 0, cj = 0;
+        if (yr) {
+            const EvalRow b = eval_row_lse(yr, K, vec, lane);
+            bad = bad || b.nan;
+            const float zy = yr[y], jy = eval_joint(xy, a.lse, zy, b.lse);
+            eval_rows_each2(xr, yr, K, vec, lane, [&](int k, float u, float v) {
+                c2 += (k != y) & ((v > zy) | ((k < y) & (v == zy)));
+                const float j = eval_joint(u, a.lse, v, b.lse);
+                cj += (k != y) & ((j > jy) | ((k < y) & (j == jy)));
+            });
+            c2 = wave_sum_i(c2);
+            cj = wave_sum_i(cj);
+        }
+        loss += bad ? (double)NAN : (double)(a.lse - xy);
+        if (!bad) {
+            hits[0] += c < 1; hits[1] += c < top;
+            if (yr) { hits[2] += c2 < 1; hits[3] += c2 < top; hits[4] += cj < 1; hits[5] += cj < top; }
+        }
+    }
+    if (lane == 0) {
+        s_loss[wave] = loss;
+        for (int i = 0; i < 6; ++i) s_hits[wave][i] = hits[i];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total = 0.0;
+        long long h[6] = {0, 0, 0, 0, 0, 0};
+        for (int w = 0; w < waves; ++w) {
+            total += s_loss[w];
+            for (int i = 0; i < 6; ++i) h[i] += s_hits[w][i];
+        }
+        state->loss_sum += total / (double)R;
+        state->calls += 1;
+        state->rows += R;
+        state->top1 += h[0];
+        state->top5 += h[1];
+        if (x2) {
+            state->dst_top1 += h[2]; state->dst_top5 += h[3];
+            state->jnt_top1 += h[4]; state->jnt_top5 += h[5];
+        }
+    }
+}
+
 // Loss step of the training loop in one pass: logits rows are in the model's internal (architecture-grouped) sample order, targets
 // in the caller's; the mean loss is accumulated into one scalar and the gradient is written in the dtype / row pitch the head's
 // backward GEMMs read (pad columns zeroed) -- no torch glue (gather, mean, add, mul, pad, cast) between the heads and the backward.
@@ -498,7 +623,7 @@ __global__ __launch_bounds__(256) void sr_resid_bwd_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int vr_version(void) { return 1000; }
+extern "C" int vr_version(void) { return 1001; }
 
 template <typename TD> static int cast_f32(const float* src, void* dst, int64_t n, vr_stream_t stream) {
     if (!src || !dst || n <= 0) return VR_EINVAL;
@@ -528,6 +653,18 @@ extern "C" int vr_softce(const float* logits, const float* target, float* loss_r
     if (!logits || !target || !loss_rows || R <= 0 || K <= 0) return VR_EINVAL;
     hipLaunchKernelGGL(softce_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target, loss_rows,
                        dlogits, R, K, gscale);
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
+
+extern "C" int vr_eval_metrics(const float* logits, const float* logits2, const int64_t* labels, int32_t R, int32_t K, int32_t ld,
+                               vr_eval_state* state, vr_stream_t stream) {
+    if (!logits || !labels || !state || R <= 0 || K <= 0 || ld < K) return VR_EINVAL;
+    if (((uintptr_t)state & 7) || ((uintptr_t)labels & 7) || ((uintptr_t)logits & 3) || ((uintptr_t)logits2 & 3)) return VR_EALIGN;
+    const int vec = ld % 4 == 0 && !((uintptr_t)logits & 15) && !((uintptr_t)logits2 & 15);
+    const int waves = R < VR_EVAL_MAX_WAVES ? R : VR_EVAL_MAX_WAVES;
+    hipLaunchKernelGGL(eval_metrics_kernel, dim3(1), dim3(64 * waves), 0, (hipStream_t)stream, logits, logits2,
+                       (const long long*)labels, R, K, ld, vec, state);
     VR_CHECK_LAUNCH();
     return VR_OK;
 }

@@ -630,13 +630,117 @@ class GraphedTrainStep:
         return loss
 
 
+class FastPath:
+    """What train_one_epoch(..., fast=FastPath()) keeps between batches and epochs: the captured steps of one (model, optimizer) pair.
+
+    A step is captured on the first batch and whenever its key changes -- batch, target and patch-target shapes, patch_output_type,
+    accum_steps, clipping on / off, compute dtype, several ranks or one, the model's arena -- after optimizer.max_norm and
+    optimizer.accum_steps were set from the epoch loop's arguments and, in the 16-bit modes, optimizer.own_shadow() was called.  One
+    rank: GraphedTrainStep(..., optimizer=optimizer, accum_steps=k), the update inside the graph, optimizer.prepare_step(apply=last)
+    before every replay.  Several ranks (grad_sync.world > 1): optimizer=None, split_for_sync=True; the final micro-step of a window
+    runs step_with_sync(..., average=False) and optimizer.step() with grad_scale / world.  At most MAX_STEPS captured steps are kept,
+    least recently used first out; a step whose arena is no longer the model's is dropped.  set_epoch (keep tables, rewiring) and
+    load_state_dict change values in place: the steps survive them and are reused across epochs.
+    The capture's eager warm-up steps leave no trace: the CPU RNG and the DropPath generator are restored by GraphedTrainStep,
+    the model's buffers (BatchNorm running statistics of the conv stems) here."""
+
+    MAX_STEPS = 2
+
+    def __init__(self):
+        self._entries = []                    # [key, arena, GraphedTrainStep], most recently used last
+        self._pair = None                     # the (optimizer, criterion) the steps were captured for
+
+    @property
+    def steps(self):
+        """The captured steps, least recently used first."""
+        return [e[2] for e in self._entries]
+
+    def validate(self, model, criterion, optimizer, device, loss_scaler, teacher_model):
+        """The fast path serves what it serves and nothing else: no silent fallback to the eager loop.  Touches no device."""
+        from .optim import FlatAdamW
+        if not isinstance(optimizer, FlatAdamW) or optimizer.model is not model:
+            raise ValueError("optimizer: fast= needs a vitres.optim.FlatAdamW constructed for this model")
+        if self._pair is None:
+            self._pair = (optimizer, criterion)
+        if self._pair[0] is not optimizer:
+            raise ValueError("optimizer: this FastPath holds steps captured for another optimizer; use one FastPath per pair")
+        if self._pair[1] is not criterion:
+            raise ValueError("criterion: this FastPath holds steps captured for another criterion; use one FastPath per pair")
+        if loss_scaler is not None:
+            raise ValueError("loss_scaler: fast= trains in bf16 or fp32 without a scaler, pass loss_scaler=None")
+        if teacher_model is not None:
+            raise ValueError("teacher_model: fast= has no teacher inside the captured step, use the eager loop for distillation")
+        if torch.device(device).type != "cuda":
+            raise ValueError("device: fast= replays a captured hipGraph and needs the GPU, got %s" % (device,))
+        p = next(model.parameters(), None)
+        if p is None or not p.is_cuda:
+            raise ValueError("model: fast= needs the model's parameters on the GPU")
+
+    def _step_for(self, model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, max_norm, accum_steps,
+                  several):
+        arena = model._ensure_arena(next(model.parameters()).device)
+        key = (tuple(samples.shape), tuple(targets.shape), None if patch_targets is None else tuple(patch_targets.shape),
+               patch_output_type, accum_steps, bool(max_norm), model.compute_dtype, several)
+        self._entries = [e for e in self._entries if e[1] is arena]
+        optimizer.max_norm = max_norm or None
+        optimizer.accum_steps = accum_steps
+        for i, e in enumerate(self._entries):
+            if e[0] == key:
+                self._entries.append(self._entries.pop(i))
+                # (the optimizer serves whichever of its graphs is replayed next; several ranks: none holds the update)
+                optimizer.serve_graph(bool(max_norm) if e[2].optimizer is not None else None)
+                return e[2]
+        del self._entries[:max(len(self._entries) - (self.MAX_STEPS - 1), 0)]
+        from . import kernels as K
+        if K.is_fast16(model.compute_dtype):
+            optimizer.own_shadow()
+        buffers = [(b, b.clone()) for b in model.buffers()]
+        step = GraphedTrainStep(model, criterion, samples, targets, patch_targets, patch_output_type,
+                                optimizer=None if several else optimizer, split_for_sync=several, accum_steps=accum_steps)
+        if several:
+            optimizer.serve_graph(None)                           # (clipping runs in optimizer.step(), after the exchange)
+        with torch.no_grad():
+            for b, saved in buffers:
+                b.copy_(saved)                                    # (the first replay drops the evaluation stem folded from them)
+        self._entries.append([key, arena, step])
+        return step
+
+    def micro_step(self, model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, epoch, train_iter,
+                   arch_sample, grad_sync, max_norm, accum_steps, micro_step):
+        """Micro-step `micro_step` of update `train_iter`: returns a device copy of the step's loss buffer (not synchronised)."""
+        several = grad_sync is not None and grad_sync.world > 1
+        step = self._step_for(model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, max_norm, accum_steps,
+                              several)
+        assert step.micro_step == micro_step, "captured step is at micro-step %d of its window, the epoch loop at %d" % (
+            step.micro_step, micro_step)
+        last = micro_step == accum_steps - 1
+        kw = dict(epoch=epoch, train_iter=train_iter, arch_sample=arch_sample)
+        if not several:
+            optimizer.prepare_step(apply=last)
+            return step(samples, targets, patch_targets, **kw).clone()
+        loss = step.step_with_sync(grad_sync, samples, targets, patch_targets, average=False, **kw).clone()
+        if last:
+            scale = optimizer.grad_scale
+            optimizer.grad_scale = scale / grad_sync.world        # the exchange left the SUM over the ranks in the arena
+            try:
+                optimizer.step()
+            finally:
+                optimizer.grad_scale = scale
+        return loss
+
+
 def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, loss_scaler=None, max_norm=0,
                     model_ema=None, mixup_fn=None, print_freq=100, teacher_model=None, hard_distill=True, alpha=0.5,
-                    logger=None, arch_sample=False, patch_mixup_fn=None, grad_sync=None, sync_every=1, accum_steps=1):
+                    logger=None, arch_sample=False, patch_mixup_fn=None, grad_sync=None, sync_every=1, accum_steps=1, fast=None):
     """accum_steps = k > 1: every k consecutive batches of the loader form one optimizer update (train_step's accum_steps /
     micro_step); the iteration index of the seed rule, the EMA update and the learning-rate meter follow the UPDATES, the loss
-    meter every micro-batch.  A trailing incomplete window is dropped (the reference's loader is drop_last)."""
+    meter every micro-batch.  A trailing incomplete window is dropped (the reference's loader is drop_last).
+    fast = a FastPath (one per (model, optimizer) pair, passed to every epoch of a run): the same loop on the captured step --
+    GraphedTrainStep with the FlatAdamW update, clipping and accumulation inside its graph -- instead of train_step; see FastPath.
+    None: the eager loop."""
     _check_accum(accum_steps)
+    if fast is not None:
+        fast.validate(model, criterion, optimizer, device, loss_scaler, teacher_model)
     kd_criterion = None
     if teacher_model is not None:                                 # engine.py:91-95: any module mapping images to logits
         kd_criterion = KnowledgeDistillationLoss(hard_distill=hard_distill)
@@ -664,9 +768,13 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
                 teacher_output = teacher_model(samples)
         if grad_sync is not None:
             grad_sync.broadcast_buffers()                         # DDP broadcast_buffers=True (main.py:367): per forward
-        loss = train_step(model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, epoch,
-                          train_iter, arch_sample, grad_sync, loss_scaler, max_norm, teacher_output=teacher_output,
-                          kd_criterion=kd_criterion, alpha=alpha, accum_steps=accum_steps, micro_step=micro_step)
+        if fast is not None:
+            loss = fast.micro_step(model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, epoch,
+                                   train_iter, arch_sample, grad_sync, max_norm, accum_steps, micro_step)
+        else:
+            loss = train_step(model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, epoch,
+                              train_iter, arch_sample, grad_sync, loss_scaler, max_norm, teacher_output=teacher_output,
+                              kd_criterion=kd_criterion, alpha=alpha, accum_steps=accum_steps, micro_step=micro_step)
         pending.append(loss)
         final = micro_step == accum_steps - 1
         if model_ema is not None and final:
@@ -719,17 +827,29 @@ def accuracy(output, target, topk=(1,)):
 
 
 @torch.no_grad()
-def evaluate(data_loader, model, device, print_freq=100, logger=None):
-    """engine.evaluate (:194-261): eval forward, CE, top-1/5 weighted by batch size, global averages."""
+def evaluate(data_loader, model, device, print_freq=100, logger=None, device_meters=None):
+    """engine.evaluate (:194-261): eval forward, CE, top-1/5 weighted by batch size, global averages.
+    device_meters: loss and hit counts accumulate in ONE vr_eval_state on the device (kernels.eval_metrics, one launch per batch, the
+    distillation head and the joint softmax of two-token models included) and are read once, after the last batch -- no torch op and
+    no device-to-host read inside the loop.  None: on when the logits are CUDA tensors; True: forced; False: the reference's torch
+    statement with its three to seven `.item()` reads per batch.  Either way the meters hold the same totals and counts."""
     criterion = torch.nn.CrossEntropyLoss()
     print_out = logger.info if logger else print
     meters = defaultdict(Meter)
     model.eval()
+    state, two_heads = None, False
     for images, target in data_loader:
         images = images.to(device, non_blocking=True)
         target = target.to(device, non_blocking=True)
         output = model(images)
         output_cls, output_dst = (output[0], output[1]) if isinstance(output, tuple) else (output, None)
+        if device_meters or (device_meters is None and output_cls.is_cuda):
+            from . import kernels as K
+            if state is None:
+                state = K.eval_state(output_cls.device)
+            two_heads = two_heads or output_dst is not None
+            K.eval_metrics(_fp32_rows(output_cls), target, state, None if output_dst is None else _fp32_rows(output_dst))
+            continue
         loss = criterion(output_cls, target)
         acc1, acc5 = accuracy(output_cls, target, topk=(1, 5))
         n = images.shape[0]
@@ -744,6 +864,15 @@ def evaluate(data_loader, model, device, print_freq=100, logger=None):
             j1, j5 = accuracy(joint, target, topk=(1, 5))
             meters['jnt_acc1'].update(j1.item(), n=n)
             meters['jnt_acc5'].update(j5.item(), n=n)
+    if state is not None:
+        from . import kernels as K
+        st = K.read_eval_state(state)                    # the evaluation's only device-to-host read
+        # loss: the unweighted mean of batch means (the reference's meter); accuracies: weighted by batch size
+        meters['loss'].total, meters['loss'].count = st['loss_sum'], st['calls']
+        for head in ('', 'dst_', 'jnt_') if two_heads else ('',):
+            for k in ('1', '5'):
+                m = meters[head + 'acc' + k]
+                m.total, m.count = 100.0 * st[head + 'top' + k], st['rows']
     for m in meters.values():
         m.synchronize_between_processes()
     info = 'Acc@1: {:.2f}, Acc@5: {:.2f}, loss: {:.2f}'.format(meters['acc1'].global_avg, meters['acc5'].global_avg,
@@ -754,6 +883,11 @@ def evaluate(data_loader, model, device, print_freq=100, logger=None):
             meters['jnt_acc5'].global_avg)
     print_out(info + '\n')
     return {k: m.global_avg for k, m in meters.items()}
+
+
+def _fp32_rows(logits):
+    """Logits as vr_eval_metrics reads them (fp32 rows; the models' heads already return these)."""
+    return logits if logits.dtype == torch.float32 else logits.float()
 
 
 def param_groups_weight_decay(model, weight_decay=0.05):

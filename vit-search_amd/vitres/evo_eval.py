@@ -65,12 +65,15 @@ def plan_for_subnet(model, sub_network_def, batch):
 
 
 @torch.no_grad()
-def score_candidate(model, sub_network_def, batches):
+def score_candidate(model, sub_network_def, batches, device_meters=None):
     """top-1 accuracy (percent, batch-size weighted -- engine.py:224-229) of one candidate on `batches`.  The keep
-    descriptor is built once per batch size and the hit count stays on the device: one host sync per candidate (the
-    reference reads `.item()` metrics every batch, engine.py:227-229)."""
+    descriptor is built once per batch size and the hit count stays on the device, in the vr_eval_state engine.evaluate uses
+    (kernels.eval_metrics: one launch per batch, no torch op on the logits): one host sync per candidate (the reference reads
+    `.item()` metrics every batch, engine.py:227-229).  device_meters as for engine.evaluate: None = on for CUDA logits; False (and
+    CPU logits, which only the host tests' kernel emulation produces) = the torch expression argmax == target, the same count."""
+    from . import kernels as K
     model.eval()
-    correct, count, plans = None, 0, {}
+    state, correct, count, plans = None, None, 0, {}
     for images, target in batches:
         b = images.shape[0]
         if b not in plans:
@@ -78,9 +81,17 @@ def score_candidate(model, sub_network_def, batches):
         out = model(images, plan=plans[b])
         # two-token (distillation) models are ranked by the distillation head's accuracy (evo_search.py:280-284: dst_acc1)
         out = (out[1] if getattr(model, "num_tokens", 1) == 2 else out[0]) if isinstance(out, tuple) else out
+        count += b
+        if device_meters or (device_meters is None and out.is_cuda):
+            if state is None:
+                state = K.eval_state(out.device)
+            # the ranked head goes in as `logits`: top1 is its exact argmax == target count, ties included
+            K.eval_metrics(out if out.dtype == torch.float32 else out.float(), target, state)
+            continue
         hits = (out.argmax(dim=1) == target).sum()
         correct = hits if correct is None else correct + hits
-        count += b
+    if state is not None:
+        correct = K.read_eval_state(state)["top1"]
     return 100.0 * float(correct) / max(count, 1) if count else 0.0
 
 

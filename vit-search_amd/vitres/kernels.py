@@ -585,6 +585,48 @@ def softce_train(logits, target, sample_map, rows_per_sample, loss_acc, grad_dty
     return d
 
 
+# vr_eval_state as int64 words: word 0 holds the bits of the double loss_sum
+EVAL_STATE_FIELDS = ("loss_sum", "calls", "rows", "top1", "top5", "dst_top1", "dst_top5", "jnt_top1", "jnt_top5", "reserved")
+
+
+def eval_state(device):
+    """A zeroed vr_eval_state in device memory (one per evaluation)."""
+    return torch.zeros(len(EVAL_STATE_FIELDS), dtype=torch.int64, device=device)
+
+
+def read_eval_state(state):
+    """The fields of a vr_eval_state as Python numbers: ONE device-to-host copy (which waits for every eval_metrics queued before it)."""
+    host = state.cpu()
+    out = dict(zip(EVAL_STATE_FIELDS, host.numpy().tolist()))
+    out["loss_sum"] = float(host[:1].view(torch.float64).numpy()[0])
+    return out
+
+
+def eval_metrics(logits, labels, state, logits2=None):
+    """vr_eval_metrics: state += {mean CE, top-1 / top-5 hits} of fp32 logits [R, K] against int64 labels [R]; with logits2 (the
+    distillation head) also its hits and those of softmax(logits) + softmax(logits2).  Nothing is read back."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.shape[0] != logits.shape[0]:
+        raise ValueError("eval_metrics: logits [R, K] and labels [R] expected, got %s and %s" % (tuple(logits.shape), tuple(labels.shape)))
+    if logits.dtype != torch.float32 or labels.dtype != torch.int64 or state.dtype != torch.int64:
+        raise TypeError("eval_metrics: fp32 logits, int64 labels and an int64 state (kernels.eval_state) expected")
+    if state.numel() != len(EVAL_STATE_FIELDS) or not state.is_contiguous():
+        raise ValueError("eval_metrics: state must come from kernels.eval_state()")
+    R, K = logits.shape
+    if logits.stride(1) != 1 and K > 1:
+        logits = logits.contiguous()
+    ld = logits.stride(0) if R > 1 else max(logits.stride(0), K)
+    if logits2 is not None:
+        if logits2.shape != logits.shape or logits2.dtype != torch.float32:
+            raise ValueError("eval_metrics: logits2 must have the shape and dtype of logits")
+        if (logits2.stride(1) != 1 and K > 1) or (R > 1 and logits2.stride(0) != ld):
+            logits2 = logits2.contiguous()
+            if ld != K:
+                logits, ld = logits.contiguous(), K
+    _lib.check(_lib.lib().vr_eval_metrics(_p(logits), _p(logits2), _p(labels.contiguous()), R, K, ld, _p(state), _stream()),
+               "vr_eval_metrics")
+    return state
+
+
 def colsum(x, out, M, N, ld, row_map=None):
     _lib.check(_lib.lib().vr_colsum(_p(x), _p(out), M, N, ld, _dt(x), _rm(row_map), _stream()), "vr_colsum")
     return out

@@ -404,7 +404,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         w = self._wc(m.weight)
         a = self._arena
         w_t, ld_t = None, 0
-        if id(m.weight) in a["tmap"]:
+        if id(m.weight) in a["tmap"] and self.compute_dtype != torch.float32:   # (an arena made in a 16-bit mode, now training in fp32)
             off_t, ld_t = a["tmap"][id(m.weight)]
             w_t = a["shadow_t"][off_t:off_t + m.weight.shape[1] * ld_t].view(m.weight.shape[1], ld_t)
         return Fn.Weights(m.weight, m.bias.detach() if m.bias is not None else None, w, w.shape[1], w_t, ld_t)

@@ -86,6 +86,12 @@ class FlatAdamW(torch.optim.Optimizer):
     def clip_enabled(self):
         return bool(_check_max_norm(self.max_norm))
 
+    def serve_graph(self, clip):
+        """Declare which captured graph the next prepare_step() / replay belongs to, for a caller that keeps several graphs of this
+        optimizer (engine.FastPath): clip = whether that graph holds the clipping launches -- prepare_step() and the replay raise
+        when max_norm disagrees with it; None = no captured graph holds the update (step() runs it after the replay)."""
+        self._graph_clip = None if clip is None else bool(clip)
+
     def _grad_factor(self):
         """What every gradient element is multiplied by: grad_scale (the caller's 1/world) / accum_steps (mean over the window)."""
         return float(self.grad_scale) / _check_accum_steps(self.accum_steps)
