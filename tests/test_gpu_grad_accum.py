@@ -338,6 +338,45 @@ def test_one_captured_graph_serves_the_whole_window(monkeypatch):
             assert rel_l2(arena4[o:o + n], ref._arena["gcur"][o:o + n]) <= GRAD_BAND
 
 
+def test_a_window_without_a_plan_buffer_stages_the_control_words_alone():
+    """accum_steps = 2 on the plain network (no supernet, no DropPath): nothing of a plan reaches the graph, the static device buffer
+    holds {clear, apply} and nothing else.  One window of the captured step against loss_and_grad(accumulate=...) x 2 + step() on an
+    identically filled twin: the quantities and bands of test_one_captured_graph_serves_the_whole_window at it == 2."""
+    crit = SoftTargetCrossEntropy()
+    mb = micro_batches(2)
+
+    def plain():
+        m = vitres.create_model("flexible_vit_sr_patch14_224_patch_output", img_size=recipe.MICRO_IMG, num_classes=recipe.MICRO_CLASSES,
+                                network_def=recipe.MICRO_DEFS[0], drop_path_rate=0.0)
+        m.load_state_dict(recipe.fill_state_dict([(k, tuple(v.shape)) for k, v in m.state_dict().items()], 100))
+        m = m.to(DEV)
+        m.set_compute_dtype(torch.bfloat16)
+        m.train()
+        opt = FlatAdamW(m, groups(m), lr=2e-3, ema_decay=0.99, accum_steps=2)
+        opt.own_shadow()
+        return m, opt
+    ref, ropt = plain()
+    ref.zero_grad(set_to_none=True)
+    for i in range(2):
+        ref.loss_and_grad(*mb[i], "seq", accumulate=i > 0)
+    ropt.step()
+    prod, opt = plain()
+    g = engine.GraphedTrainStep(prod, crit, *mb[0], "seq", optimizer=opt, accum_steps=2)
+    assert g.keep_static is None and g._ctl_all.numel() == 2
+    start = _snapshot(prod, opt)
+    for i in range(2):
+        assert g.micro_step == i
+        opt.prepare_step(apply=(g.micro_step == g.accum_steps - 1))
+        g(*mb[i], epoch=31, train_iter=0, arch_sample=None)
+        after = _snapshot(prod, opt)
+        if i == 0:                                                # the non-final replay changes nothing but the gradient arena
+            assert all(torch.equal(a, b) for a, b in zip(start, after))
+    assert g.micro_step == 0 and opt._step == 1 and not torch.equal(start[0], after[0])
+    print("parameters %.3g, EMA %.3g (band 2e-3)" % (rel(after[0], ref._arena["flat"]), rel(after[3], ropt._flat_state["ema"])))
+    assert rel(after[0], ref._arena["flat"]) < 2e-3 and rel(after[3], ropt._flat_state["ema"]) < 2e-3
+    assert torch.equal(after[4].float(), after[0].bfloat16().float())
+
+
 class _LaunchLog:
     def __init__(self, real, log):
         self._real, self._log = real, log

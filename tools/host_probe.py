@@ -24,12 +24,7 @@ for i in range(n + 5):
         torch.cuda.synchronize(); T.clear()
     t0 = time.perf_counter(); torch.randperm(64); torch.randperm(64); tick("mixup draws", t0)
     t0 = time.perf_counter(); rng = torch.random.get_rng_state(); plan = model.sample_plan(128); torch.random.set_rng_state(rng); tick("sample_plan (+rng save/restore)", t0)
-    t0 = time.perf_counter(); flat, _ = model.plan_host_buffer(plan); tick("plan_host_buffer", t0)
-    t0 = time.perf_counter()
-    slot = g._stage[g._stage_i % len(g._stage)]; g._stage_i += 1
-    if slot[1] is not None: slot[1].synchronize()
-    slot[0].numpy()[:] = flat; g.keep_static.copy_(slot[0], non_blocking=True); slot[1] = torch.cuda.Event(); slot[1].record()
-    tick("staging copy", t0)
+    t0 = time.perf_counter(); g._inputs.upload(model, plan, True, True); tick("plan_host_buffer + staging copy", t0)
     t0 = time.perf_counter(); g._gather(x, plan); tick("gather launch", t0)
     t0 = time.perf_counter(); g.graph.replay(); tick("graph.replay", t0)
     t0 = time.perf_counter(); opt.step(); tick("opt.step", t0)

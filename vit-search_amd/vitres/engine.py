@@ -9,6 +9,8 @@ Differences, all deliberate: bf16 compute needs no GradScaler (loss_scaler may b
 ranks are averaged by one flat all-reduce (GradSync) instead of DDP buckets; the non-finite-loss check is
 done on the device and read back every `sync_every` iterations (reference: every iteration).
 """
+import contextlib
+import functools
 import math
 import sys
 import time
@@ -16,6 +18,10 @@ from collections import defaultdict
 
 import torch
 import torch.distributed as dist
+
+from . import functional as Fn, kernels as K, stem
+from .losses import SoftTargetCrossEntropy
+from .optim import FlatAdamW, _check_accum_steps
 
 
 def is_dist():
@@ -138,7 +144,6 @@ class GradSync:
     @staticmethod
     def _to_wire(src, dst):
         if src.is_cuda and dst.dtype == torch.bfloat16:
-            from . import kernels as K
             K.cast_bf16(src, dst)              # vr_cast_f32_bf16: round-to-nearest-even, 16-byte accesses
         else:
             dst.copy_(src)
@@ -212,6 +217,30 @@ class KnowledgeDistillationLoss(torch.nn.Module):
                                                               ', soft_temperature={}'.format(self.soft_temperature))
 
 
+@contextlib.contextmanager
+def _arch_seed(arch_sample, epoch, train_iter):
+    """The reference's `arch_sample` seed rule around a forward (engine.py:119-131, 164-165); the CPU RNG state is back on exit."""
+    if arch_sample is None:
+        yield
+        return
+    rng = torch.random.get_rng_state()
+    if arch_sample in ('single', 'hybrid'):
+        torch.manual_seed(epoch * 10000 + train_iter)
+    elif arch_sample != 'multi':
+        raise ValueError('arch_sample has invalid value {}.'.format(arch_sample))
+    try:
+        yield
+    finally:
+        torch.random.set_rng_state(rng)
+
+
+def _patch_loss(criterion, cls_pred, patch_pred, targets, patch_targets, patch_output_type):
+    """criterion(cls) + criterion(patch): per token against the patch targets ('seq') or of the mean token against the targets ('avg')."""
+    if patch_output_type not in ('seq', 'avg'):
+        raise ValueError()
+    return criterion(cls_pred, targets) + criterion(patch_pred, patch_targets if patch_output_type == 'seq' else targets)
+
+
 def train_step(model, criterion, optimizer, samples, targets, patch_targets=None, patch_output_type=None, epoch=0,
                train_iter=0, arch_sample=None, grad_sync=None, loss_scaler=None, max_norm=None, average_grads=True,
                teacher_output=None, kd_criterion=None, alpha=0.5, accum_steps=1, micro_step=0):
@@ -230,30 +259,16 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
     torch.nn.utils.clip_grad_norm_.  Either way after the all-reduce, so every rank clips the same averaged gradients."""
     accum_steps = _check_accum(accum_steps, micro_step)
     last = micro_step == accum_steps - 1
-    rng = None
-    if arch_sample is not None:                                   # engine.py:119-131
-        rng = torch.random.get_rng_state()
-        if arch_sample in ('single', 'hybrid'):
-            torch.manual_seed(epoch * 10000 + train_iter)
-        elif arch_sample != 'multi':
-            raise ValueError('arch_sample has invalid value {}.'.format(arch_sample))
-    if patch_targets is None:
-        outputs = model(samples)
-        output_cls, output_dst = (outputs[0], outputs[1]) if isinstance(outputs, tuple) else (outputs, outputs)
-        loss = criterion(output_cls, targets)
-        if teacher_output is not None:
-            loss = loss * (1 - alpha) + kd_criterion(output_dst, teacher_output) * alpha
-    else:
-        cls_pred, patch_pred = model(samples, patch_output_type=patch_output_type)
-        loss = criterion(cls_pred, targets)
-        if patch_output_type == 'seq':
-            loss = loss + criterion(patch_pred, patch_targets)
-        elif patch_output_type == 'avg':
-            loss = loss + criterion(patch_pred, targets)
+    with _arch_seed(arch_sample, epoch, train_iter):
+        if patch_targets is None:
+            outputs = model(samples)
+            output_cls, output_dst = (outputs[0], outputs[1]) if isinstance(outputs, tuple) else (outputs, outputs)
+            loss = criterion(output_cls, targets)
+            if teacher_output is not None:
+                loss = loss * (1 - alpha) + kd_criterion(output_dst, teacher_output) * alpha
         else:
-            raise ValueError()
-    if rng is not None:
-        torch.random.set_rng_state(rng)                           # engine.py:164-165
+            cls_pred, patch_pred = model(samples, patch_output_type=patch_output_type)
+            loss = _patch_loss(criterion, cls_pred, patch_pred, targets, patch_targets, patch_output_type)
     if micro_step == 0:
         optimizer.zero_grad(set_to_none=True)
     if accum_steps > 1:
@@ -302,8 +317,7 @@ def train_step(model, criterion, optimizer, samples, targets, patch_targets=None
 
 
 def _check_accum(accum_steps, micro_step=0):
-    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
-        raise ValueError("accum_steps must be an int >= 1, got %r" % (accum_steps,))
+    _check_accum_steps(accum_steps)
     if not 0 <= micro_step < accum_steps:
         raise ValueError("micro_step must lie in 0..accum_steps-1, got %r" % (micro_step,))
     return accum_steps
@@ -319,6 +333,68 @@ def _window(micro_step, accum_steps):
 # stalls the device for ~1 ms (six 8.3 - 8.9 ms steps among the first 26 of a run, none after).  RUN_AHEAD replays in
 # flight keep the device fed with the host two steps ahead from the third step on.
 RUN_AHEAD = 2
+
+
+def _cuts(model, n):
+    """The first n backward cuts of model.split_plan(parts >= 3) as a list (shorter when the layout has fewer); [] for none."""
+    cuts = model.split_plan(parts=max(n + 1, 3)) if n >= 1 else None
+    return cuts[:n] if cuts else []
+
+
+@contextlib.contextmanager
+def _rng_preserved(model):
+    """The CPU generator and the model's private DropPath generator are, on exit, where they were on entry."""
+    # the warm-up steps and the capture's plan must not advance the streams a checkpoint restored (the first replay then continues
+    # exactly where the saved run stopped)
+    rng, dp_rng = torch.random.get_rng_state(), model.drop_path_rng_state()
+    try:
+        yield
+    finally:
+        torch.random.set_rng_state(rng)
+        model.set_drop_path_rng_state(dp_rng)
+
+
+class _ReplayInputs:
+    """The ONE static int32 device buffer through which what the host makes per replay reaches the graph, and its staging ring."""
+    # buf = the keep rows of every ChannelDrop and the DropPath scale vectors (bit-cast floats) of the replay's plan
+    # (model.plan_host_buffer) and, behind them when accum_steps > 1, the control words {clear, apply} of the update window: one
+    # staging copy per replay serves both.  No plan words and no window: no buffer, no ring, upload() does nothing.
+    # upload() goes through a ring of pinned staging blocks: the host runs several replays ahead of the device, a single block would
+    # be overwritten before its copy has executed.  The copy is a small KERNEL reading the pinned block, not a memcpy: a
+    # hipMemcpyAsync crosses to the copy engine and back, 28 against 15 us of GPU time per step.
+    RING = 64
+
+    def __init__(self, model, plan, accum_steps, device):
+        flat, self.nk = model.plan_host_buffer(plan)
+        self.n_plan = flat.size
+        n = flat.size + (2 if accum_steps > 1 else 0)
+        self.buf = self.plan = self.ctl = None
+        self._ring, self._next = [], 0
+        if not n:
+            return
+        self.buf = torch.ones(n, dtype=torch.int32, device=device)       # (the control words start as {1, 1})
+        if flat.size:
+            self.buf[:flat.size].copy_(torch.from_numpy(flat))
+            self.plan = self.buf[:flat.size]
+        if accum_steps > 1:
+            self.ctl = self.buf[flat.size:]
+        self._ring = [[torch.empty(n, dtype=torch.int32).pin_memory(), None] for _ in range(self.RING)]
+
+    def upload(self, model, plan, first, last):
+        """The words of `plan` and {clear, apply} = {first, last} -> the next staging block -> the device buffer (stream-ordered)."""
+        if self.buf is None:
+            return
+        block = self._ring[self._next % self.RING]
+        self._next += 1
+        if block[1] is not None:
+            block[1].synchronize()                                # the host runs ahead of the device: the block's last copy is done?
+        host = block[0].numpy()
+        if self.plan is not None:
+            host[:self.n_plan] = model.plan_host_buffer(plan)[0]
+        if self.ctl is not None:
+            host[self.n_plan], host[self.n_plan + 1] = int(first), int(last)
+        K.copy_i32_from_pinned(block[0], self.buf)
+        block[1] = torch.cuda.current_stream().record_event()
 
 
 class GraphedTrainStep:
@@ -342,23 +418,22 @@ class GraphedTrainStep:
         step_with_sync() can all-reduce the finished tail of the gradient arena (most of the parameters) while the rest
         of the backward -- most of the time -- is still running.
         opt_overlap / opt_overlap_blocks (with optimizer): number of arena ranges updated early, beside the rest of the backward,
-        and the workgroup cap of those updates (see below).  With optimizer.max_norm set at capture no parameter may change before
-        the whole gradient norm is known: the early launches then are the SUMS OF SQUARES of those ranges (same stream, ranges and
-        cap), and the remaining range's sum, the finish and ONE full-width AdamW follow the backward.  The replays follow
+        and the workgroup cap of those updates (see _capture_update).  With optimizer.max_norm set at capture no parameter may change
+        before the whole gradient norm is known: the early launches then are the SUMS OF SQUARES of those ranges (same stream, ranges
+        and cap), and the remaining range's sum, the finish and ONE full-width AdamW follow the backward.  The replays follow
         optimizer.max_norm from value to value (float("inf"): measure only); switching it on or off after the capture makes
         optimizer.prepare_step() raise.
         accum_steps: micro-batches per optimizer update (class docstring).  With optimizer= the caller calls
         optimizer.prepare_step(apply=(step.micro_step == accum_steps - 1)) before every replay."""
         self.accum_steps = _check_accum(accum_steps)
         self.micro_step = 0
-        if hasattr(model, "_check_fp16_eval"):
-            model._check_fp16_eval(True)          # (fp16 is an evaluation mode: nothing is captured or launched)
+        model._check_fp16_eval(True)              # (fp16 is an evaluation mode: nothing is captured or launched)
         self.model, self.criterion, self.pot = model, criterion, patch_output_type
         self.graph_b, self.split, self.more_graphs, self.ranges = None, None, [], []
         self._inflight = []
-        # optimizer (a vitres.optim.FlatAdamW, single rank): the update becomes part of the graph -- the arena tail (last stage +
-        # heads, most parameters) is updated on the side stream as soon as its gradients are final, beside the rest of the
-        # backward; the remainder after it.  Call optimizer.prepare_step() before every replay instead of optimizer.step().
+        self.exposed = None                  # bench.py: a list here collects (backward done, exchange done) event pairs
+        # optimizer (a vitres.optim.FlatAdamW, single rank): the update becomes part of the graph (_capture_update).  Call
+        # optimizer.prepare_step() before every replay instead of optimizer.step().
         self.optimizer = optimizer if (optimizer is not None and hasattr(optimizer, "step_device")) else None
         if self.optimizer is not None and split_for_sync:
             raise ValueError("optimizer-in-graph is for one rank; with a gradient exchange step the optimizer after step_with_sync")
@@ -367,152 +442,115 @@ class GraphedTrainStep:
             self.optimizer.accum_steps = self.accum_steps             # the update uses the window's mean
         # soft-target CE is the training loss of every shipped recipe (main.py:390-398): the whole step then runs without
         # autograd and without torch glue between the heads and the backward (model.loss_and_grad / vr_softce_train)
-        from .losses import SoftTargetCrossEntropy
         self.fused_loss = isinstance(criterion, SoftTargetCrossEntropy) and hasattr(model, "loss_and_grad")
         self.x, self.t = samples.clone(), targets.clone()
         self.pt = patch_targets.clone() if patch_targets is not None else None
-        B = samples.shape[0]
-        rng = torch.random.get_rng_state()
-        # the DropPath draws come from the model's private generator: the warm-up steps and the capture's plan must not advance the
-        # stream a checkpoint restored (the first replay then continues exactly where the saved run stopped)
-        dp_rng = model.drop_path_rng_state() if hasattr(model, "drop_path_rng_state") else None
+        with _rng_preserved(model):
+            self._warm_up(warmup)
+            plan = model.sample_plan(samples.shape[0])
+            self._static_inputs(samples, plan)
+            model.zero_grad(set_to_none=True)
+            self.graph = torch.cuda.CUDAGraph()
+            K.ensure_workspaces(samples.device, roles=(0, 1))         # stream-K workspaces exist before anything is captured
+            self._loss_buf = torch.zeros(1, dtype=torch.float32, device=samples.device)
+            clip = self.optimizer.prepare_capture() if self.optimizer is not None else False
+            # the backward is cut for ONE of two reasons.  split_for_sync = number of backward parts (True = 2): part k's graph is
+            # followed by the all-reduce of the arena range it completed, overlapping part k+1.  optimizer: opt_overlap ranges are
+            # updated early, the parts follow one another in the same capture
+            parts = 2 if split_for_sync is True else int(split_for_sync or 0)
+            cuts = _cuts(model, opt_overlap if self.optimizer is not None else parts - 1)
+            if cuts and self.optimizer is None:
+                self.split = cuts[0]
+            with model.backward_capture(split=[c for c, _ in cuts] or None, join_parts=not cuts or self.optimizer is None,
+                                        clear_gate=None if self._ctl is None else self._ctl[0:1]):
+                self._capture_step(plan, cuts, clip, opt_overlap_blocks)
+                self._capture_rest(cuts)
+        self.loss = self.loss.detach()
+
+    def _warm_up(self, steps):
+        """Eager steps on a side stream before the capture (arena, LDS attributes, allocator)."""
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):                              # eager warm-up (arena, LDS attributes, allocator)
-            for _ in range(warmup):
-                model.zero_grad(set_to_none=True)
+        with torch.cuda.stream(side):
+            for _ in range(steps):
+                self.model.zero_grad(set_to_none=True)
                 self._step_body(None)
         torch.cuda.current_stream().wait_stream(side)
-        plan = model.sample_plan(B)
-        # what changes per replay reaches the graph through ONE static int32 buffer: the keep rows of every ChannelDrop and the
-        # DropPath scale vectors (bit-cast floats), both made on the host (model.plan_host_buffer) and uploaded from a ring of
-        # pinned staging blocks; for the type-0 patch embedding the patch gather runs in front of the graph, straight from the
-        # caller's batch (no copy of the images into a static buffer, no re-ordering pass)
-        self.keep_static = None                                   # (name kept: tests / tools look at it)
-        self._plan_nk, self._stage, self._stage_i = 0, [], 0
-        flat, nk = model.plan_host_buffer(plan)
-        self._ctl_all = self._ctl = None
-        if self.accum_steps > 1:
-            # the control words {clear, apply} ride behind the plan in ONE device buffer: one staging copy per replay serves both
-            self._ctl_all = torch.ones(flat.size + 2, dtype=torch.int32, device=samples.device)
-            self._ctl = self._ctl_all[flat.size:]
-            self._plan_nk = nk
-            if flat.size:
-                self._ctl_all[:flat.size].copy_(torch.from_numpy(flat))
-                self.keep_static = self._ctl_all[:flat.size]
-            self._stage = [[torch.empty(flat.size + 2, dtype=torch.int32).pin_memory(), None] for _ in range(64)]
-        elif flat.size:
-            self.keep_static = torch.from_numpy(flat).to(samples.device)
-            self._plan_nk = nk
-            self._stage = [[torch.empty(flat.size, dtype=torch.int32).pin_memory(), None] for _ in range(64)]
-        self.col_static = None
-        if getattr(model, "embed_type", None) == 0 and model.compute_dtype == torch.bfloat16:
+
+    def _static_inputs(self, samples, plan):
+        """The static device buffers the replays write besides x / t / pt: the plan + control words, the patchify operand."""
+        self._inputs = _ReplayInputs(self.model, plan, self.accum_steps, samples.device)
+        self.keep_static, self._ctl = self._inputs.plan, self._inputs.ctl             # (names kept: tests / tools look at them)
+        self._ctl_all = self._inputs.buf if self._ctl is not None else None
+        # for the type-0 patch embedding the patch gather runs in front of the graph, straight from the caller's batch (no copy of
+        # the images into a static buffer, no re-ordering pass)
+        model, self.col_static = self.model, None
+        if model.embed_type == 0 and model.compute_dtype == torch.bfloat16:
             ldk = (model.in_chans * model.patch_size ** 2 + 7) // 8 * 8
-            self.col_static = torch.empty((B * model.patch_embed.num_patches, ldk), dtype=torch.bfloat16, device=samples.device)
+            self.col_static = torch.empty((samples.shape[0] * model.patch_embed.num_patches, ldk), dtype=torch.bfloat16,
+                                          device=samples.device)
             self._gather(samples, plan)
-        model.zero_grad(set_to_none=True)
-        # split_for_sync = number of backward parts (True = 2): part k's graph is followed by the all-reduce of the arena range
-        # it completed, overlapping part k+1 (a cut in front of every spatial reduction, counted from the end)
-        parts = 2 if split_for_sync is True else int(split_for_sync or 0)
-        cuts = None
-        if parts >= 2:
-            cuts = model.split_plan(parts=max(parts, 3))
-            cuts = cuts[:parts - 1] if cuts else None
-        if cuts:
-            self.split = cuts[0]
-        self.graph = torch.cuda.CUDAGraph()
-        from . import kernels as K
-        K.ensure_workspaces(samples.device, roles=(0, 1))             # stream-K workspaces exist before anything is captured
-        model._bwd_split = [c for c, _ in cuts] if cuts else None
-        gate_apply = None
-        if self._ctl is not None:
-            model._clear_gate = self._ctl[0:1]                     # the arena's clear inside the capture reads `clear` at run time
-            gate_apply = self._ctl[1:2]
-        try:
-            self._loss_buf = torch.zeros(1, dtype=torch.float32, device=samples.device)
-            opt_cut = None
-            clip = False
+
+    def _capture_step(self, plan, cuts, clip, cap):
+        """self.graph: forward + loss + the first backward part and, with an optimizer, the other parts and the update."""
+        with torch.cuda.graph(self.graph):
+            if self.keep_static is not None:
+                self.model.attach_plan_buffer(plan, self.keep_static, self._inputs.nk)
+            plan.embed_col = self.col_static
+            self.loss = self._step_body(plan)
             if self.optimizer is not None:
-                clip = bool(getattr(self.optimizer, "clip_enabled", lambda: False)())
-                self.optimizer._graph_clip = None
-                self.optimizer.prepare_step()                      # allocates / fills the device hyper-parameters (not captured)
-                self.optimizer._step -= 1
-                self.optimizer._graph_clip = clip                  # (prepare_step() raises once max_norm no longer matches)
-                if clip:
-                    self.optimizer._clip["used"] = 0
-                # opt_overlap = number of arena ranges updated EARLY (0 off, 1 (default): head + last stage, 2: + the stage
-                # before; measured round 4: 7.47 -> 7.36 - 7.39 ms with 1 or 2, profiles/r04_optimizer_overlap.txt):
-                # the backward is cut in front of the spatial reductions (model.split_plan) and the range a part completes is
-                # updated on the weight gradients' side stream -- IN ORDER with the groups there: a third branch would land on
-                # their hardware queue in front of them (round 4) -- by at most opt_overlap_blocks resident workgroups
-                # (256: one per CU; the uncapped update took the chip and cost more than it hid in rounds 1 - 3), beside the rest
-                # of the backward; what is left (the first stage + embedding) follows the backward at full width.
-                if opt_overlap > 0:
-                    oc = model.split_plan(parts=max(opt_overlap + 1, 3))
-                    oc = oc[:opt_overlap] if isinstance(oc, list) else None
-                    if oc:
-                        opt_cut = oc
-                        model._bwd_split = [c for c, _ in oc]
-                        model._bwd_join_parts = False              # the next part follows in the same capture
-            with torch.cuda.graph(self.graph):
-                if self.keep_static is not None:
-                    model.attach_plan_buffer(plan, self.keep_static, self._plan_nk)
-                plan.embed_col = self.col_static
-                self.loss = self._step_body(plan)
-                if self.optimizer is not None:
-                    from . import functional as Fn
-                    n_arena = model._arena["flat"].numel()
-                    if opt_cut is not None and getattr(model, "_bwd_state", None) is not None:
-                        hi = n_arena
-                        for _, lo in opt_cut:                          # ranges complete from the arena's end backwards
-                            if clip:                                   # (each range fills its own slice of the partial sums)
-                                piece = self.optimizer.reserve_norm_slice(lo, hi)
-                                early = lambda lo=lo, hi=hi, piece=piece, cap=opt_overlap_blocks if Fn.OVERLAP else 0: \
-                                    self.optimizer.norm_range_device(lo, hi, piece, max_blocks=cap, gate=gate_apply)  # noqa: E731
-                            else:
-                                early = lambda lo=lo, hi=hi, cap=opt_overlap_blocks if Fn.OVERLAP else 0: \
-                                    self.optimizer.step_device(lo, hi, max_blocks=cap)                    # noqa: E731
-                            if Fn.OVERLAP:
-                                Fn.on_side(early)
-                            else:
-                                early()
-                            hi = lo
-                            if getattr(model, "_bwd_state", None) is not None:
-                                model.resume_backward()
-                    else:
-                        hi = n_arena
-                    if clip:
-                        # the last backward part joined the side stream: every early sum is complete in stream order
-                        self.optimizer.norm_range_device(0, hi, self.optimizer.reserve_norm_slice(0, hi), gate=gate_apply)
-                        self.optimizer.clip_finish_device(gate=gate_apply)
-                        self.optimizer.step_device(0, n_arena, clip=True)
-                    else:
-                        self.optimizer.step_device(0, hi)
-            while getattr(model, "_bwd_state", None) is not None:
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self.graph.pool()):
+                self._capture_update(cuts, clip, cap)
+
+    def _capture_update(self, cuts, clip, cap):
+        """The in-graph optimizer sequence, issued into the running capture behind the first backward part (clip: see __init__)."""
+        # The arena tail (last stage + heads, most parameters) is updated on the side stream as soon as its gradients are final, beside
+        # the rest of the backward; the remainder after it.  opt_overlap = len(cuts) = number of arena ranges updated EARLY (0 off, 1
+        # (default): head + last stage, 2: + the stage before; measured round 4: 7.47 -> 7.36 - 7.39 ms with 1 or 2,
+        # profiles/r04_optimizer_overlap.txt): the backward is cut in front of the spatial reductions (model.split_plan) and the range
+        # a part completes is updated on the weight gradients' side stream -- IN ORDER with the groups there: a third branch would land
+        # on their hardware queue in front of them (round 4) -- by at most `cap` = opt_overlap_blocks resident workgroups (256: one per
+        # CU; the uncapped update took the chip and cost more than it hid in rounds 1 - 3), beside the rest of the backward; what is
+        # left (the first stage + embedding) follows the backward at full width.
+        opt, model = self.optimizer, self.model
+        gate = None if self._ctl is None else self._ctl[1:2]       # `apply`, read at run time by the gated norm launches
+        cap = cap if Fn.OVERLAP else 0
+        hi = n_arena = model._arena["flat"].numel()
+        if model._bwd_state is not None:
+            for _, lo in cuts:                                     # ranges complete from the arena's end backwards
+                if clip:                                           # (each range fills its own slice of the partial sums)
+                    early = functools.partial(opt.norm_range_device, lo, hi, opt.reserve_norm_slice(lo, hi), max_blocks=cap,
+                                              gate=gate)
+                else:
+                    early = functools.partial(opt.step_device, lo, hi, max_blocks=cap)
+                if Fn.OVERLAP:
+                    Fn.on_side(early)
+                else:
+                    early()
+                hi = lo
+                if model._bwd_state is not None:
                     model.resume_backward()
-                self.more_graphs.append(g)
-        finally:
-            model._bwd_split = None
-            model._bwd_join_parts = True
-            if self._ctl is not None:
-                model._clear_gate = None
+        if clip:
+            # the last backward part joined the side stream: every early sum is complete in stream order
+            opt.norm_range_device(0, hi, opt.reserve_norm_slice(0, hi), gate=gate)
+            opt.clip_finish_device(gate=gate)
+            opt.step_device(0, n_arena, clip=True)
+        else:
+            opt.step_device(0, hi)
+
+    def _capture_rest(self, cuts):
+        """The backward parts still pending, one graph each (more_graphs), and the arena range every part completes (ranges)."""
+        while self.model._bwd_state is not None:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self.graph.pool()):
+                self.model.resume_backward()
+            self.more_graphs.append(g)
         if self.more_graphs:
             self.graph_b = self.more_graphs[0]
-            end = model._arena["gcur"].numel()
-            for _, start in cuts:                                  # arena range completed by part 1, 2, ... (the rest: last part)
-                self.ranges.append((start, end))
-                end = start
-            self.ranges.append((0, end))
-        self.loss = self.loss.detach()
-        torch.random.set_rng_state(rng)
-        if dp_rng is not None:
-            model.set_drop_path_rng_state(dp_rng)
+            bounds = [self.model._arena["gcur"].numel()] + [start for _, start in cuts] + [0]
+            self.ranges = list(zip(bounds[1:], bounds[:-1]))       # arena range completed by part 1, 2, ... (the rest: last part)
 
     def _gather(self, samples, plan):
         """Patch gather of the caller's batch into the graph's static patchify operand (internal, arch-grouped sample order)."""
-        from . import kernels as K
         smap = None
         if plan.order is not None:
             smap, _ = self.model._order_tensors(plan.order, samples.device)
@@ -523,7 +561,7 @@ class GraphedTrainStep:
         """forward + loss + (first part of the) backward of one step; returns the loss tensor."""
         if self.fused_loss:
             return self.model.loss_and_grad(self.x, self.t, self.pt, self.pot, plan=plan,
-                                            loss_out=getattr(self, "_loss_buf", None) if plan is not None else None)
+                                            loss_out=self._loss_buf if plan is not None else None)
         loss = self._loss(self.model(self.x, patch_output_type=self.pot, plan=plan))
         loss.backward()
         return loss
@@ -531,45 +569,22 @@ class GraphedTrainStep:
     def _loss(self, out):
         if self.pt is None:
             return self.criterion(out[0] if isinstance(out, tuple) else out, self.t)
-        cls_pred, patch_pred = out
-        return self.criterion(cls_pred, self.t) + self.criterion(patch_pred, self.pt if self.pot == 'seq' else self.t)
+        return _patch_loss(self.criterion, out[0], out[1], self.t, self.pt, self.pot)
 
     def __call__(self, samples, targets, patch_targets=None, epoch=0, train_iter=0, arch_sample=None):
-        if hasattr(self.model, "_check_fp16_eval"):
-            self.model._check_fp16_eval(True)     # (the model was switched to fp16 after the capture: no replay)
-        if self.optimizer is not None and getattr(self.optimizer, "_graph_clip", None) is not None and \
-                self.optimizer.clip_enabled() != self.optimizer._graph_clip:
-            raise RuntimeError("optimizer.max_norm was switched %s after this step's graph was captured: the replay would ignore it"
-                               % ("on" if self.optimizer.clip_enabled() else "off"))
-        rng = None
-        if arch_sample is not None:                                # engine.py:119-131
-            rng = torch.random.get_rng_state()
-            if arch_sample in ('single', 'hybrid'):
-                torch.manual_seed(epoch * 10000 + train_iter)
-            elif arch_sample != 'multi':
-                raise ValueError('arch_sample has invalid value {}.'.format(arch_sample))
-        plan = self.model.sample_plan(samples.shape[0])
-        if rng is not None:
-            torch.random.set_rng_state(rng)
+        self._replay(None, samples, targets, patch_targets, epoch, train_iter, arch_sample)
+        return self.loss
+
+    def _replay(self, grad_sync, samples, targets, patch_targets=None, epoch=0, train_iter=0, arch_sample=None):
+        """One replay of the step on the caller's batch.  grad_sync (step_with_sync): on the final micro-step of a window the arena
+        range a backward part completed is all-reduced right behind that part's replay, beside the next part's; returns those works."""
+        self.model._check_fp16_eval(True)         # (the model was switched to fp16 after the capture: no replay)
+        if self.optimizer is not None:
+            self.optimizer.check_graph_clip()
+        with _arch_seed(arch_sample, epoch, train_iter):
+            plan = self.model.sample_plan(samples.shape[0])
         first, last, following = _window(self.micro_step, self.accum_steps)
-        if self.keep_static is not None or self._ctl_all is not None:
-            slot = self._stage[self._stage_i % len(self._stage)]
-            self._stage_i += 1
-            if slot[1] is not None:
-                slot[1].synchronize()                             # the host runs ahead of the device: the block's last copy is done?
-            host = slot[0].numpy()
-            n_plan = 0
-            if self.keep_static is not None:
-                flat, _ = self.model.plan_host_buffer(plan)
-                n_plan = flat.size
-                host[:n_plan] = flat
-            if self._ctl_all is not None:                         # {clear, apply} of this replay
-                host[n_plan], host[n_plan + 1] = int(first), int(last)
-            from . import kernels as K
-            # (a kernel reading pinned memory, not a memcpy)
-            K.copy_i32_from_pinned(slot[0], self._ctl_all if self._ctl_all is not None else self.keep_static.view(-1))
-            slot[1] = torch.cuda.Event()
-            slot[1].record()
+        self._inputs.upload(self.model, plan, first, last)
         if self.col_static is not None:
             self._gather(samples, plan)                           # reads the caller's tensor directly
         elif samples.data_ptr() != self.x.data_ptr():
@@ -581,23 +596,19 @@ class GraphedTrainStep:
         if len(self._inflight) >= RUN_AHEAD:                       # (bounded run-ahead: RUN_AHEAD)
             self._inflight.pop(0).synchronize()
         self.graph.replay()
-        self.model._stem_fold = None                               # (stem.drop_fold: the replay moved BatchNorm's running statistics)
+        stem.drop_fold(self.model)                                 # (the replay moved BatchNorm's running statistics)
+        works = []
         for k, g in enumerate(self.more_graphs):
-            if self._sync is not None and last:                   # the arena range of the part just replayed is final: exchange it now
-                self._works.append(self._sync.all_reduce_range(*self.ranges[k]))
+            if grad_sync is not None and last:                    # the arena range of the part just replayed is final: exchange it now
+                works.append(grad_sync.all_reduce_range(*self.ranges[k]))
             g.replay()
-        e_done = torch.cuda.Event()
-        e_done.record()
-        self._inflight.append(e_done)
+        self._inflight.append(torch.cuda.current_stream().record_event())
         self.micro_step = following
-        return self.loss
+        return works
 
     def finish_update(self):
         """No-op: every replay's optimizer update is complete with the replay itself (kept for callers that call it before
         evaluating, checkpointing or changing the learning rate, as the removed deferred update required)."""
-
-    _sync, _works = None, ()
-    _inflight = None
 
     def step_with_sync(self, grad_sync, samples, targets, patch_targets=None, average=True, **kw):
         """Replay + data-parallel gradient exchange: with split_for_sync the all-reduce of the last stage's gradients
@@ -605,29 +616,23 @@ class GraphedTrainStep:
         summed -- for an optimizer that applies 1/world itself).  accum_steps > 1: only the final micro-step of a window exchanges
         (the window's summed gradients; the optimizer's accum_steps divides); the others issue no collective at all."""
         _, last, _ = _window(self.micro_step, self.accum_steps)
-        self._sync, self._works = grad_sync, []
-        try:
-            loss = self(samples, targets, patch_targets, **kw)
-        finally:
-            self._sync = None
+        works = self._replay(grad_sync, samples, targets, patch_targets, **kw)
         if not last:
-            self._works = ()
-            return loss
+            return self.loss
         ev = None
-        if getattr(self, "exposed", None) is not None and grad_sync.world > 1:
+        if self.exposed is not None and grad_sync.world > 1:
             ev = torch.cuda.Event(enable_timing=True)
             ev.record()                                           # the backward is complete here (on the compute stream)
         if self.more_graphs:
-            self._works.append(grad_sync.all_reduce_range(*self.ranges[-1]))
-            grad_sync.finish(self._works, average=average)
+            works.append(grad_sync.all_reduce_range(*self.ranges[-1]))
+            grad_sync.finish(works, average=average)
         else:
             grad_sync.all_reduce_grads(average=average)
         if ev is not None:
             ev1 = torch.cuda.Event(enable_timing=True)
             ev1.record()                                          # work.wait() made the compute stream wait for the exchange
             self.exposed.append((ev, ev1))
-        self._works = ()
-        return loss
+        return self.loss
 
 
 class FastPath:
@@ -657,7 +662,6 @@ class FastPath:
 
     def validate(self, model, criterion, optimizer, device, loss_scaler, teacher_model):
         """The fast path serves what it serves and nothing else: no silent fallback to the eager loop.  Touches no device."""
-        from .optim import FlatAdamW
         if not isinstance(optimizer, FlatAdamW) or optimizer.model is not model:
             raise ValueError("optimizer: fast= needs a vitres.optim.FlatAdamW constructed for this model")
         if self._pair is None:
@@ -691,7 +695,6 @@ class FastPath:
                 optimizer.serve_graph(bool(max_norm) if e[2].optimizer is not None else None)
                 return e[2]
         del self._entries[:max(len(self._entries) - (self.MAX_STEPS - 1), 0)]
-        from . import kernels as K
         if K.is_fast16(model.compute_dtype):
             optimizer.own_shadow()
         buffers = [(b, b.clone()) for b in model.buffers()]
@@ -751,6 +754,14 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
     meters = defaultdict(Meter)
     arch_sample = arch_sample or None
     pending = []
+
+    def drain():                                                  # device -> host sync (reference: every iteration)
+        for v in (torch.stack(pending).tolist() if pending else []):
+            if not math.isfinite(v):
+                print_out('Loss is {}, stopping training'.format(v))
+                sys.exit(1)
+            meters['loss'].update(v)
+        pending.clear()
     t0 = time.time()
     for step_i, (samples, targets) in enumerate(_full_windows(data_loader, accum_steps, print_out)):
         train_iter, micro_step = divmod(step_i, accum_steps)      # train_iter: the optimizer update's index
@@ -780,23 +791,14 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         if model_ema is not None and final:
             model_ema.update(model)
         if len(pending) >= sync_every:
-            for v in torch.stack(pending).tolist():               # device -> host sync (reference: every iteration)
-                if not math.isfinite(v):
-                    print_out('Loss is {}, stopping training'.format(v))
-                    sys.exit(1)
-                meters['loss'].update(v)
-            pending = []
+            drain()
         if not final:
             continue
         meters['lr'].update(optimizer.param_groups[0]['lr'])
         if print_freq and train_iter % print_freq == 0:
             print_out('Epoch: [{}] [{}] loss: {:.4f} time: {:.1f}s'.format(epoch, train_iter, meters['loss'].global_avg,
                                                                           time.time() - t0))
-    for v in (torch.stack(pending).tolist() if pending else []):
-        if not math.isfinite(v):
-            print_out('Loss is {}, stopping training'.format(v))
-            sys.exit(1)
-        meters['loss'].update(v)
+    drain()
     for m in meters.values():
         m.synchronize_between_processes()
     print_out('Averaged stats: ' + '  '.join('{}: {:.6f}'.format(k, m.global_avg) for k, m in meters.items()))
@@ -844,7 +846,6 @@ def evaluate(data_loader, model, device, print_freq=100, logger=None, device_met
         output = model(images)
         output_cls, output_dst = (output[0], output[1]) if isinstance(output, tuple) else (output, None)
         if device_meters or (device_meters is None and output_cls.is_cuda):
-            from . import kernels as K
             if state is None:
                 state = K.eval_state(output_cls.device)
             two_heads = two_heads or output_dst is not None
@@ -865,7 +866,6 @@ def evaluate(data_loader, model, device, print_freq=100, logger=None, device_met
             meters['jnt_acc1'].update(j1.item(), n=n)
             meters['jnt_acc5'].update(j5.item(), n=n)
     if state is not None:
-        from . import kernels as K
         st = K.read_eval_state(state)                    # the evaluation's only device-to-host read
         # loss: the unweighted mean of batch means (the reference's meter); accuracies: weighted by batch size
         meters['loss'].total, meters['loss'].count = st['loss_sum'], st['calls']

@@ -12,6 +12,8 @@ Execution model
   * all ChannelDrop prefix masks of a forward are sampled on the host first (bit-exact reference RNG
     protocol), shipped as one int32 [n_masks, B] tensor and consumed by kernel epilogues.
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -149,6 +151,9 @@ class _ViTResFn(torch.autograd.Function):
 class FlexibleDistillVisionTransformerSR(nn.Module):
     _PATCH_SIZES = (14,)
     _ALWAYS_DST_HEAD = False          # the patch-16 sibling registers dst_head even without a distillation token
+    # how the next backward is run: set for the duration of a capture by backward_capture(), read by _run_backward / _bwd_loop
+    # (_bwd_state: the pending parts of a backward that _bwd_split cut, run by resume_backward)
+    _bwd_split, _bwd_join_parts, _clear_gate, _bwd_state = None, True, None, None
 
     def __init__(self, img_size=224, patch_size=14, in_chans=3, num_classes=1000, drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0., norm_layer=MaskedLayerNorm, distill_token=True, network_def=None,
@@ -417,8 +422,8 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         if cached is None or cached[0] != buf.numel():
             cached = a["zero_ranges"] = (buf.numel(), [(0, buf.numel())], 0)
         if buf.is_cuda:
-            # _clear_gate (engine.GraphedTrainStep(accum_steps > 1) sets it around its capture): the clear is decided per replay
-            K.zero_ranges(buf, cached[1], gate=getattr(self, "_clear_gate", None))
+            # _clear_gate (backward_capture: engine.GraphedTrainStep(accum_steps > 1)): the clear is decided per replay
+            K.zero_ranges(buf, cached[1], gate=self._clear_gate)
         else:
             for lo, hi in cached[1]:
                 buf[lo:hi].zero_()
@@ -981,7 +986,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         keep = bool(getattr(self, "_acc_keep", False)) and not fresh      # loss_and_grad(accumulate=True): add in place
         a["gcur"] = a["gflat"] if (fresh or keep) else torch.zeros_like(a["flat"])
         # the arena may hold earlier micro-steps' sums: the writers that go through a temporary add instead of storing
-        self._acc_add = keep or getattr(self, "_clear_gate", None) is not None
+        self._acc_add = keep or self._clear_gate is not None
         if fresh and not a.pop("gzeroed", False):      # (the forward may have zeroed it on the side stream already)
             self._zero_grad_arena(a["gcur"], plan.batch)
         a["gzeroed"] = False
@@ -997,7 +1002,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
               "ready": ready}
         # _bwd_split = j: stop after the head and blocks[j:]; the rest runs in resume_backward() (a second hipGraph, so that the
         # all-reduce of the finished tail of the gradient arena overlaps it -- engine.GraphedTrainStep)
-        cuts = getattr(self, "_bwd_split", None)
+        cuts = self._bwd_split
         cuts = [] if cuts is None else ([cuts] if isinstance(cuts, int) else list(cuts))
         stops = []
         for cut in cuts:                   # head + the entries of blocks[cut:] form a prefix of the reversed tape
@@ -1008,6 +1013,19 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
         self._bwd_loop(st, st["stops"].pop(0))
         self._bwd_state = st if st["i"] < len(st["rtape"]) else None
         return [self._gview(p) for p in params]
+
+    @contextlib.contextmanager
+    def backward_capture(self, split=None, join_parts=True, clear_gate=None):
+        """Steer the backwards run inside the block (engine.GraphedTrainStep, around its capture); the defaults are back on exit."""
+        # split: block indices at which the backward stops, in descending order (_bwd_split; resume_backward() runs the next part).
+        # join_parts=False: a part does not wait for the side stream at its stop -- the next part follows in the same capture.
+        # clear_gate: a device int32 word read at run time; 0 keeps what the gradient arena holds (accumulation window), and every
+        # gradient writer adds in place.
+        self._bwd_split, self._bwd_join_parts, self._clear_gate = split, join_parts, clear_gate
+        try:
+            yield self
+        finally:
+            self._bwd_split, self._bwd_join_parts, self._clear_gate = None, True, None
 
     def resume_backward(self):
         """Next part of a backward that was split by _bwd_split (gradients land in the same arena views); returns True while
@@ -1166,7 +1184,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             Fn.on_aux("tail", Fn.flush_ln_grads)   #  runs a third branch on the weight gradients' queue, IN FRONT of the last groups)
         else:
             Fn.flush_ln_grads()            # LayerNorm weight / bias gradients of this part: partial rows -> arena
-        if stop >= len(rtape) or getattr(self, "_bwd_join_parts", True):
+        if stop >= len(rtape) or self._bwd_join_parts:
             Fn.join_side()                 # weight-gradient GEMMs trail on the side stream (functional.on_side); an intermediate
                                            # stop joins too unless the next part follows in the same capture (_bwd_join_parts)
         st["i"], st["g"], st["gt"] = stop, g, gt

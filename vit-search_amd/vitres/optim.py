@@ -16,7 +16,7 @@ import math
 
 import torch
 
-from . import _lib
+from . import _lib, stem
 from .kernels import _p, _stream
 
 MAX_GROUPS = 16
@@ -91,6 +91,25 @@ class FlatAdamW(torch.optim.Optimizer):
         optimizer (engine.FastPath): clip = whether that graph holds the clipping launches -- prepare_step() and the replay raise
         when max_norm disagrees with it; None = no captured graph holds the update (step() runs it after the replay)."""
         self._graph_clip = None if clip is None else bool(clip)
+
+    def check_graph_clip(self):
+        """A graph holds the clipping launches or not from its capture on: raises once max_norm was switched between on and off
+        after it (prepare_step() and every replay ask; on <-> float("inf") is the switch a captured graph follows)."""
+        if self._graph_clip is not None and self.clip_enabled() != self._graph_clip:
+            raise RuntimeError("FlatAdamW.max_norm was %s after the step's graph was captured %s the clipping launches: a replay "
+                               "would ignore it.  Capture with max_norm set (float('inf') measures without clipping) and switch "
+                               "between values, or capture a new GraphedTrainStep."
+                               % (("set", "without") if self.clip_enabled() else ("cleared", "with")))
+
+    def prepare_capture(self):
+        """Before a capture of step_device() / norm_range_device() launches (engine.GraphedTrainStep): fills the device blocks they read
+        WITHOUT counting a step, hands the partial-sum slices out from the first again; returns whether the graph is to clip."""
+        clip = self._graph_clip = self.clip_enabled()      # (a graph captured earlier with the other setting has no say any more)
+        self.prepare_step()
+        self._step -= 1
+        if clip:
+            self._clip["used"] = 0
+        return clip
 
     def _grad_factor(self):
         """What every gradient element is multiplied by: grad_scale (the caller's 1/world) / accum_steps (mean over the window)."""
@@ -211,7 +230,7 @@ class FlatAdamW(torch.optim.Optimizer):
         if g is None or p0.grad is None or p0.grad.data_ptr() != g.data_ptr() + 4 * a["offsets"][0][0]:
             raise RuntimeError("FlatAdamW needs the gradients in the model's flat arena (one backward since zero_grad)")
         self._step += 1
-        self.model._stem_fold = None           # parameters change through raw pointers: no Tensor._version moves (stem.drop_fold)
+        stem.drop_fold(self.model)             # parameters change through raw pointers: no Tensor._version moves
         arr = self._group_structs(self._step)
         st = self._flat_state
         shadow = a["shadow"] if self.model.compute_dtype == torch.bfloat16 else None
@@ -249,11 +268,7 @@ class FlatAdamW(torch.optim.Optimizer):
         contains step_device() launches (engine.GraphedTrainStep(optimizer=...)).  With max_norm set, max_norm and grad_scale
         are uploaded too; a graph holds the clipping launches or not from its capture on, so switching max_norm between on and
         off after the capture raises here (on <-> float("inf") is the switch a captured graph follows)."""
-        if self._graph_clip is not None and self.clip_enabled() != self._graph_clip:
-            raise RuntimeError("FlatAdamW.max_norm was %s after the step's graph was captured %s the clipping launches: a replay "
-                               "would ignore it.  Capture with max_norm set (float('inf') measures without clipping) and switch "
-                               "between values, or capture a new GraphedTrainStep."
-                               % (("set", "without") if self.clip_enabled() else ("cleared", "with")))
+        self.check_graph_clip()
         a = self._bind()
         dev = a["flat"].device
         if getattr(self, "_hp_dev", None) is None or self._hp_dev.device != dev:
@@ -261,7 +276,7 @@ class FlatAdamW(torch.optim.Optimizer):
         host = torch.zeros(MAX_GROUPS * 8, dtype=torch.float32)
         if apply:
             self._step += 1
-            self.model._stem_fold = None       # parameters change through raw pointers: no Tensor._version moves (stem.drop_fold)
+            stem.drop_fold(self.model)         # parameters change through raw pointers: no Tensor._version moves
             arr = self._group_structs(self._step)
             vals = [getattr(arr[gi], n) for gi in range(len(self.param_groups)) for n, _ in _Group._fields_]
             host[:len(vals)] = torch.tensor(vals, dtype=torch.float32)
@@ -288,7 +303,7 @@ class FlatAdamW(torch.optim.Optimizer):
             raise ValueError("range must be non-empty and aligned to 8 elements")
         st = self._flat_state
         shadow = a["shadow"] if self.model.compute_dtype == torch.bfloat16 else None
-        self.model._stem_fold = None           # (stem.drop_fold)
+        stem.drop_fold(self.model)
 
         def at(t, esz):
             return None if t is None else t.data_ptr() + lo * esz
@@ -299,13 +314,11 @@ class FlatAdamW(torch.optim.Optimizer):
                                                      at(st["ema"], 4), float(self.ema_decay or 0.0), st["gid"].data_ptr() + lo // 8,
                                                      _p(self._hp_dev), 1, len(self.param_groups), hi - lo, _p(self._clip["state"]),
                                                      int(max_blocks), _stream()), "vr_adamw_flat_clip")
-            if shadow is not None:
-                a["shadow_ok"] = True
-            return
-        _lib.check(_lib.lib().vr_adamw_flat_dev_capped(at(a["flat"], 4), at(g, 4), at(st["m"], 4), at(st["v"], 4), at(shadow, 2),
-                                                       at(st["ema"], 4), float(self.ema_decay or 0.0), st["gid"].data_ptr() + lo // 8,
-                                                       _p(self._hp_dev), len(self.param_groups), hi - lo, int(max_blocks), _stream()),
-                   "vr_adamw_flat_dev_capped")
+        else:
+            _lib.check(_lib.lib().vr_adamw_flat_dev_capped(
+                at(a["flat"], 4), at(g, 4), at(st["m"], 4), at(st["v"], 4), at(shadow, 2), at(st["ema"], 4), float(self.ema_decay or 0.0),
+                st["gid"].data_ptr() + lo // 8, _p(self._hp_dev), len(self.param_groups), hi - lo, int(max_blocks), _stream()),
+                "vr_adamw_flat_dev_capped")
         if shadow is not None:
             a["shadow_ok"] = True
 
