@@ -125,8 +125,9 @@ __device__ __forceinline__ float gsum(float v) {
 // other.  Register pressure is bounded by construction: the forward walks the keys in blocks of PB tile pairs with a
 // running (max, sum) and one accumulator rescale per block (the scores of a block, not of the whole row, live in registers);
 // the backward kernels hold one key / query tile per wave.  exp(x) is v_exp_f32 on x * log2(e) folded into the scale;
-// zero-padded LDS rows make every mask of the backward kernels redundant (an out-of-range key or query contributes exact
-// zeros), the forward masks the one partial key tile only.
+// zero-padded LDS rows make the masks of the key-tile phases redundant (an out-of-range query has zero Q and dO rows and
+// lse = delta = 0: P = 1, dS = 0; an out-of-range key is a column that is never stored); the forward and the query-tile phases
+// of the backward mask the one partial key tile only (scores to -inf / P to 0: a padded key's P is exp(-lse), not bounded).
 // The padded row count NP = 32 * NKP is a compile-time constant: every LDS fragment address is one per-lane base (computed
 // once per kernel) plus an immediate -- PMC counters of the previous form showed 935 VALU instructions per 16-query tile,
 // half of them address arithmetic, on a kernel whose VALU pipe was busy 3.6x longer than its matrix pipe.
@@ -361,7 +362,9 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dq_kernel(const bf16_t* __re
         f32x4 dq[AC<D>::DT];
 #pragma unroll
         for (int dt = 0; dt < AC<D>::DT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-        // keys beyond N are zero rows of K and V in LDS: their dS is finite and meets a zero K^T fragment -- no masks
+        // keys beyond N are zero rows of K and V in LDS, so their score is 0 and their P would be exp(-lse): finite only while
+        // lse > -88.7.  A head whose logits are all below that (ordinary data: softmax is shift invariant) made P = inf, dS = +-inf
+        // and inf * 0 = NaN against the zero K^T fragment.  P of those slots is therefore masked to 0; dS = 0 then meets the zero rows.
 #pragma unroll
         for (int kp = 0; kp < NKP; ++kp) {
             if (FULL || kp * 32 < N) {
@@ -376,8 +379,15 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dq_kernel(const bf16_t* __re
                             sc = mfma16(I::cread(kb[dk], k0), qf[dk], sc);
                             dp = mfma16(I::cread(vb[dk], k0), gf[dk], dp);
                         }
+                        // the tiles that can hold key slots >= N (fwd_kernel's choice: under FULL the last pair, at compile time):
+                        // their exponent is forced to -1e30, P = 0 (see the note above the key loop of bwd_dq_kernel)
+                        const bool tail = FULL ? (2 * kp + tt >= 2 * NKP - 2) : (k0 + 16 > N);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) sc[r] = ex2(fmaf(sc[r], cs, -l2)) * ((dp[r] - dl) * scale);
+                        for (int r = 0; r < 4; ++r) {
+                            float x = fmaf(sc[r], cs, -l2);
+                            if (tail) x = (k0 + 4 * g + r) < N ? x : -1e30f;
+                            sc[r] = ex2(x) * ((dp[r] - dl) * scale);
+                        }
                     }
                     ds[tt] = sc;
                 }
@@ -470,7 +480,8 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_dkv_kernel(const bf16_t* __r
             dka[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
             dva[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        // queries beyond N are zero rows of Q and dO in LDS (and Ls = Ds = 0): P is finite, dS = 0 -- no masks
+        // queries beyond N are zero rows of Q and dO in LDS (and Ls = Ds = 0): P = exp2(0) = 1, dS = 0 -- no masks.  Keys beyond N
+        // (zero kf / vf) are columns of the accumulators that are never stored; the MFMA keeps columns apart.
 #pragma unroll(NKP <= 3 ? NKP : 1)
         for (int qp = 0; qp < nqp; ++qp) {
             f32x4 p[2], ds[2];
@@ -678,8 +689,15 @@ __global__ __launch_bounds__(NW * 64, OCC) void bwd_short_kernel(const bf16_t* _
                             sc = mfma16(I::cread(kb[dk], k0), qf[dk], sc);
                             dp = mfma16(I::cread(vb[dk], k0), gf[dk], dp);
                         }
+                        // the tiles that can hold key slots >= N (fwd_kernel's choice: under FULL the last pair, at compile time):
+                        // their exponent is forced to -1e30, P = 0 (see the note above the key loop of bwd_dq_kernel)
+                        const bool tail = FULL ? (2 * kp + tt >= 2 * NKP - 2) : (k0 + 16 > N);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) sc[r] = ex2(fmaf(sc[r], cs, -l2)) * ((dp[r] - dl) * scale);
+                        for (int r = 0; r < 4; ++r) {
+                            float x = fmaf(sc[r], cs, -l2);
+                            if (tail) x = (k0 + 4 * g + r) < N ? x : -1e30f;
+                            sc[r] = ex2(x) * ((dp[r] - dl) * scale);
+                        }
                     }
                     ds[tt] = sc;
                 }
