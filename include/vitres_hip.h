@@ -427,6 +427,26 @@ int vr_token_mix(const float* samples, float* out, const int64_t* labels, const 
                  float lam_img, float oml_img, float on_value, float off_value, vr_stream_t stream);
 
 /*
+ * The uint8 input side (the reference's datasets.build_dataloader: timm fast_collate + PrefetchLoader -- uint8 NCHW batches,
+ * normalised on the GPU by `input.float().sub_(mean).div_(std)` with mean / std = the 0..1 constants * 255).
+ *   n(u, c) = (float(u) - mean[c]) / std[c], a correctly rounded IEEE division (no reciprocal): bit-identical with that
+ *   statement on the CPU.  mean / std: HOST pointers to C floats, copied into the kernel arguments (no device buffer); C <= 4.
+ * vr_normalize_u8:  out[b,c,y,x] = n(in[b,c,y,x], c); in uint8, out fp32, both contiguous [B,C,H,W].
+ * vr_token_mix_u8:  vr_token_mix on uint8 samples -- bit-identical with vr_normalize_u8 followed by vr_token_mix (the box takes
+ *   n(partner pixel), the image-level half mixes n(own) and n(partner) with separately rounded products), same targets and patch
+ *   targets, every other argument as vr_token_mix.  One pass: each uint8 element is read once, the partner only where it is used.
+ * Both: W % 4 == 0 (else VR_EUNSUPPORTED); in 4-byte and out 16-byte aligned (else VR_EALIGN); a lane takes 16 pixels when
+ * W % 16 == 0 and in is 16-byte aligned, 4 otherwise.  Arguments are validated before anything is launched.
+ */
+int vr_normalize_u8(const uint8_t* in, float* out, int32_t B, int32_t C, int32_t H, int32_t W, const float* mean,
+                    const float* std, vr_stream_t stream);
+int vr_token_mix_u8(const uint8_t* samples, float* out, const int64_t* labels, const int64_t* partner, float* targets,
+                    float* patch_targets, int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_classes, int32_t patch_len,
+                    int32_t half, int32_t y0, int32_t y1, int32_t x0, int32_t x1, float lam_patch, float oml_patch,
+                    float lam_img, float oml_img, float on_value, float off_value, const float* mean, const float* std,
+                    vr_stream_t stream);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

@@ -1,0 +1,154 @@
+"""What the input side of one training batch costs, in front of the captured step of bench.py's default workload (sr_tiny supernet,
+B = 128, 3 x 224 x 224, patch_len 4, K = 1000, bf16): the fp32 path as it stands against the uint8 path of
+SwitchTokenMix(input_norm=...) mixing straight into the step's static inputs.
+
+  a   pinned fp32 host batch -> device; vr_token_mix into fresh tensors; the three copy_ into the step's static x / t / pt
+      (train_one_epoch with a patch_mixup_fn that does not write into the step: GraphedTrainStep._replay's copies)
+  b   pinned uint8 host batch -> device; vr_token_mix_u8 into the step's static x / t / pt (no copy at replay)
+  c   vr_normalize_u8 alone, device-resident uint8 -> fp32 (the evaluation side: ResidentU8Batches)
+
+One process, the three lines alternating; every timed stage is followed by an untimed replay of the captured step, so each stage
+starts from the caches a training step leaves behind.  HIP events bracket the host-to-device copy and the device work of every
+stage; per line the MEDIAN over --iters batches after --warmup.  GB/s = the bytes the line must move (from the shapes and the fixed
+draw: a 2 x 2 box of the 4 x 4 grid, so the partner is read for 1/4 of the first half and all of the second) over its time.  Before
+timing, a and b are checked to leave the same bits in x / t / pt.
+
+    python tools/input_bench.py [--iters 60] [--warmup 10] [--out FILE]"""
+import argparse
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "vit-search_amd"))
+
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+
+PL, NC = 4, 1000
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("input_bench.py times the GPU path and needs the MI355X")
+    from vitres import engine, kernels as K
+    from vitres.losses import SoftTargetCrossEntropy
+    from vitres.optim import FlatAdamW
+    from vitres.token_mixup import SwitchTokenMix
+    dev = torch.device("cuda:0")
+    B = bench.WORKLOADS["sr_tiny_supernet"]["batch"]
+    mean, std = K.IMAGENET_DEFAULT_MEAN, K.IMAGENET_DEFAULT_STD
+
+    # host batches: the fp32 one is the uint8 one normalised on the CPU (timm's statement), both pinned
+    g = torch.Generator().manual_seed(0)
+    u8_host = torch.randint(0, 256, (B, 3, 224, 224), dtype=torch.uint8, generator=g)
+    m255 = torch.tensor([x * 255 for x in mean]).view(1, 3, 1, 1)
+    s255 = torch.tensor([x * 255 for x in std]).view(1, 3, 1, 1)
+    f32_host = u8_host.float().sub_(m255).div_(s255).pin_memory()
+    u8_host = u8_host.pin_memory()
+    labels = torch.randint(0, NC, (B,), generator=g).to(dev)
+    h = B // 2
+    draw = dict(half=h, partner=torch.cat([torch.randperm(h, generator=g), torch.randperm(B - h, generator=g) + h]),
+                box=(1, 3, 1, 3), lam_patch=1 - 4 / 16, lam_img=0.37)
+    mix_f, mix_u = SwitchTokenMix(PL, num_classes=NC), SwitchTokenMix(PL, num_classes=NC, input_norm=(mean, std))
+
+    # the captured step whose static inputs are the destination
+    torch.manual_seed(0)
+    model, _ = bench.build_model("sr_tiny_supernet", torch.bfloat16, dev)
+    model.train()
+    model.set_epoch(31)
+    opt = FlatAdamW(model, engine.param_groups_weight_decay(model, 0.05), lr=5e-4 * B / 512.0)
+    opt.own_shadow()
+    x0, t0, pt0, _ = mix_f(f32_host.to(dev), labels, draw=draw)
+    step = engine.GraphedTrainStep(model, SoftTargetCrossEntropy(), x0, t0, pt0, "seq", optimizer=opt)
+    u8_dev, norm_out = u8_host.to(dev), torch.empty((B, 3, 224, 224), device=dev)
+    it = [0]
+
+    def replay():
+        opt.prepare_step()
+        step(step.x, step.t, step.pt, epoch=31, train_iter=it[0], arch_sample="multi")
+        it[0] += 1
+
+    def stage_a(ev):
+        ev[0].record()
+        s = f32_host.to(dev, non_blocking=True)
+        ev[1].record()
+        xs, t, pt, _ = mix_f(s, labels, draw=draw)
+        step.x.copy_(xs, non_blocking=True)
+        step.t.copy_(t, non_blocking=True)
+        step.pt.copy_(pt, non_blocking=True)
+        ev[2].record()
+
+    def stage_b(ev):
+        ev[0].record()
+        s = u8_host.to(dev, non_blocking=True)
+        ev[1].record()
+        mix_u(s, labels, out=step.x, targets_out=step.t, patch_targets_out=step.pt, draw=draw)
+        ev[2].record()
+
+    def stage_c(ev):
+        ev[0].record()
+        ev[1].record()
+        K.normalize_u8(u8_dev, mean, std, out=norm_out)
+        ev[2].record()
+
+    # same bits (a against b against c) before any timing
+    evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    stage_a(evs)
+    want = [step.x.clone(), step.t.clone(), step.pt.clone()]
+    for buf in (step.x, step.t, step.pt):
+        buf.zero_()
+    stage_b(evs)
+    same = all(torch.equal(a, b) for a, b in zip(want, (step.x, step.t, step.pt)))
+    stage_c(evs)
+    same = same and torch.equal(norm_out.cpu(), f32_host)
+    if not same:
+        sys.exit("input_bench.py: the uint8 path does not reproduce the fp32 path's bits")
+
+    N = B * 3 * 224 * 224
+    T = 4 * (B * NC + B * PL * PL * NC)                           # targets + patch targets, fp32
+    partner = (0.25 * h + (B - h)) / B                            # share of the batch whose partner pixel is read
+    lines = [("a fp32 H2D + vr_token_mix + 3 copy_", stage_a, 4 * N, (1 + partner) * 4 * N + 4 * N + T + 2 * (4 * N + T)),
+             ("b uint8 H2D + vr_token_mix_u8 in place", stage_b, N, (1 + partner) * N + 4 * N + T),
+             ("c vr_normalize_u8 alone", stage_c, 0, N + 4 * N)]
+    times = {name: ([], []) for name, _, _, _ in lines}
+    for i in range(args.warmup + args.iters):
+        for name, fn, _, _ in lines:
+            evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            fn(evs)
+            replay()
+            torch.cuda.synchronize()
+            if i >= args.warmup:
+                times[name][0].append(evs[0].elapsed_time(evs[1]))
+                times[name][1].append(evs[1].elapsed_time(evs[2]))
+    out = ["input stage per batch: B = %d, 3 x 224 x 224, patch_len %d, K = %d, sr_tiny supernet (bf16 step replayed between stages); "
+           "median of %d after %d warm-up, HIP events; x / t / pt of a and b bit-identical" % (B, PL, NC, args.iters, args.warmup)]
+    med = {}
+    for name, _, host_bytes, dev_bytes in lines:
+        h2d, work = statistics.median(times[name][0]), statistics.median(times[name][1])
+        total = statistics.median([p + q for p, q in zip(*times[name])])
+        med[name[0]] = total
+        lo, hi = min(p + q for p, q in zip(*times[name])), max(p + q for p, q in zip(*times[name]))
+        row = "%-40s total %7.3f ms (min %.3f max %.3f)" % (name, total, lo, hi)
+        if host_bytes:
+            row += " | H2D %6.1f MB %7.3f ms %6.1f GB/s" % (host_bytes / 1e6, h2d, host_bytes / h2d / 1e6)
+        row += " | device %6.1f MB %7.3f ms %7.1f GB/s" % (dev_bytes / 1e6, work, dev_bytes / work / 1e6)
+        out.append(row)
+    out.append("b / a = %.3f (%s)" % (med["b"] / med["a"], "b is faster" if med["b"] < med["a"] else "b is NOT faster"))
+    text = "\n".join(out)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -68,7 +68,151 @@ __global__ __launch_bounds__(256) void mix_targets_kernel(const int64_t* __restr
     }
 }
 
+// ---- uint8 input side: timm's fast_collate batches (uint8 NCHW), normalised on the device as its PrefetchLoader does
+// (input.float().sub_(mean).div_(std), mean / std = the 0..1 constants * 255).  n(u, c) = (float(u) - mean[c]) / std[c] with
+// the correctly rounded division hipcc emits by default (v_div_scale / v_div_fmas / v_div_fixup; no fast-math flag on this
+// file): bit-identical with the CPU statement.  A lane takes V = 16 pixels (one 16-byte load, four 16-byte stores) when the
+// row length and the pointer allow it, V = 4 otherwise; the 4x smaller read is why the normaliser rides in the mixer.
+struct NormParams {
+    float mean[4], std[4];
+};
+
+__device__ __forceinline__ float pick4(const float (&v)[4], int c) {      // (a per-lane index into kernel arguments: selects, no scratch)
+    return c == 0 ? v[0] : c == 1 ? v[1] : c == 2 ? v[2] : v[3];
+}
+
+__device__ __forceinline__ float norm1(uint32_t u, float m, float s) { return ((float)u - m) / s; }
+
+template <int V>
+struct U8Vec;
+template <>
+struct U8Vec<4> {
+    uint32_t w[1];
+    __device__ __forceinline__ void load(const uint8_t* p) { w[0] = *reinterpret_cast<const uint32_t*>(p); }
+};
+template <>
+struct U8Vec<16> {
+    uint32_t w[4];
+    __device__ __forceinline__ void load(const uint8_t* p) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
+};
+template <int V>
+__device__ __forceinline__ uint32_t u8_at(const U8Vec<V>& v, int i) { return (v.w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+
+template <int V>
+__global__ __launch_bounds__(256) void normalize_u8_kernel(const uint8_t* __restrict__ in, float* __restrict__ out, long long total,
+                                                           int hwv, int C, NormParams np) {
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int c = (int)((idx / hwv) % C);
+        const float m = pick4(np.mean, c), s = pick4(np.std, c);
+        U8Vec<V> a;
+        a.load(in + idx * V);
+#pragma unroll
+        for (int q = 0; q < V / 4; ++q)
+            *reinterpret_cast<float4*>(out + idx * V + 4 * q) =
+                make_float4(norm1(u8_at(a, 4 * q), m, s), norm1(u8_at(a, 4 * q + 1), m, s), norm1(u8_at(a, 4 * q + 2), m, s),
+                            norm1(u8_at(a, 4 * q + 3), m, s));
+    }
+}
+
+// mix_samples_kernel on uint8 pixels: the choice partner / own is made on the bytes (n(chosen) == chosen n), the second half
+// normalises both and mixes them as mix2 does.  The partner is read only where it is used.
+template <int V>
+__global__ __launch_bounds__(256) void mix_samples_u8_kernel(const uint8_t* __restrict__ in, float* __restrict__ out,
+                                                             const int64_t* __restrict__ partner, int B, int C, int H, int W,
+                                                             int half, int py0, int py1, int px0, int px1, float lam, float oml,
+                                                             NormParams np) {
+    const int wv = W / V;
+    const long long per = (long long)C * H * wv, total = (long long)B * per;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const int b = (int)(idx / per);
+        const long long r = idx % per;
+        const int x = (int)(r % wv) * V, yrow = (int)((r / wv) % H), c = (int)(r / ((long long)wv * H));
+        const long long off = (long long)b * C * H * W + r * V;
+        const long long poff = (long long)partner[b] * C * H * W + r * V;
+        const float m = pick4(np.mean, c), s = pick4(np.std, c);
+        U8Vec<V> a, p;
+        a.load(in + off);
+        p = a;
+        float o[V];
+        if (b < half) {
+            const bool box = yrow >= py0 && yrow < py1 && x + V - 1 >= px0 && x < px1;
+            if (box) p.load(in + poff);
+#pragma unroll
+            for (int i = 0; i < V; ++i) {
+                const bool take = box && x + i >= px0 && x + i < px1;
+                o[i] = norm1(take ? u8_at(p, i) : u8_at(a, i), m, s);
+            }
+        } else {
+            p.load(in + poff);
+#pragma unroll
+            for (int i = 0; i < V; ++i) o[i] = mix2(norm1(u8_at(a, i), m, s), lam, norm1(u8_at(p, i), m, s), oml);
+        }
+#pragma unroll
+        for (int q = 0; q < V / 4; ++q)
+            *reinterpret_cast<float4*>(out + off + 4 * q) = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    }
+}
+
+inline unsigned stream_blocks(long long total) {
+    const long long blocks = (total + 255) / 256;
+    return (unsigned)(blocks > 16384 ? 16384 : blocks);
+}
+
+inline NormParams norm_params(const float* mean, const float* std, int C) {
+    NormParams np;
+    for (int c = 0; c < 4; ++c) {
+        np.mean[c] = c < C ? mean[c] : 0.f;
+        np.std[c] = c < C ? std[c] : 1.f;
+    }
+    return np;
+}
+
 }  // namespace
+
+extern "C" int vr_normalize_u8(const uint8_t* in, float* out, int32_t B, int32_t C, int32_t H, int32_t W, const float* mean,
+                               const float* std, vr_stream_t stream) {
+    if (!in || !out || !mean || !std) return VR_EINVAL;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return VR_EINVAL;
+    if (C > 4 || W % 4) return VR_EUNSUPPORTED;
+    if (((uintptr_t)in & 3) || ((uintptr_t)out & 15)) return VR_EALIGN;
+    const NormParams np = norm_params(mean, std, C);
+    const long long n = (long long)B * C * H * W;
+    if (W % 16 == 0 && !((uintptr_t)in & 15))
+        hipLaunchKernelGGL(normalize_u8_kernel<16>, dim3(stream_blocks(n / 16)), dim3(256), 0, (hipStream_t)stream, in, out, n / 16,
+                           H * (W / 16), C, np);
+    else
+        hipLaunchKernelGGL(normalize_u8_kernel<4>, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, in, out, n / 4,
+                           H * (W / 4), C, np);
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
+
+extern "C" int vr_token_mix_u8(const uint8_t* samples, float* out, const int64_t* labels, const int64_t* partner, float* targets,
+                               float* patch_targets, int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_classes,
+                               int32_t patch_len, int32_t half, int32_t y0, int32_t y1, int32_t x0, int32_t x1, float lam_patch,
+                               float oml_patch, float lam_img, float oml_img, float on_value, float off_value, const float* mean,
+                               const float* std, vr_stream_t stream) {
+    if (!samples || !out || !labels || !partner || !targets || !patch_targets || !mean || !std) return VR_EINVAL;
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || num_classes <= 0 || patch_len <= 0 || half < 0 || half > B) return VR_EINVAL;
+    if (C > 4 || W % 4 || H % patch_len || W % patch_len) return VR_EUNSUPPORTED;
+    if (((uintptr_t)samples & 3) || ((uintptr_t)out & 15)) return VR_EALIGN;
+    const NormParams np = norm_params(mean, std, C);
+    const int psy = H / patch_len, psx = W / patch_len;
+    const long long n = (long long)B * C * H * W;
+    if (W % 16 == 0 && !((uintptr_t)samples & 15))
+        hipLaunchKernelGGL(mix_samples_u8_kernel<16>, dim3(stream_blocks(n / 16)), dim3(256), 0, (hipStream_t)stream, samples, out,
+                           partner, B, C, H, W, half, psy * y0, psy * y1, psx * x0, psx * x1, lam_img, oml_img, np);
+    else
+        hipLaunchKernelGGL(mix_samples_u8_kernel<4>, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, samples, out,
+                           partner, B, C, H, W, half, psy * y0, psy * y1, psx * x0, psx * x1, lam_img, oml_img, np);
+    hipLaunchKernelGGL(mix_targets_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, labels, partner, targets, patch_targets,
+                       num_classes, patch_len, half, y0, y1, x0, x1, lam_patch, oml_patch, lam_img, oml_img, on_value, off_value);
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
 
 extern "C" int vr_token_mix(const float* samples, float* out, const int64_t* labels, const int64_t* partner, float* targets,
                             float* patch_targets, int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_classes,

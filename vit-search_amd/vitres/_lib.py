@@ -90,6 +90,8 @@ SYMBOLS = {
     "vr_conv_w_flip": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p],
     "vr_conv1_direct": [c_void_p] * 4 + [c_int32] * 6 + [c_void_p],
     "vr_token_mix": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p],
+    "vr_normalize_u8": [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p, c_void_p],
+    "vr_token_mix_u8": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p, c_void_p, c_void_p],
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],

@@ -1,0 +1,95 @@
+"""The uint8 input side (reference datasets.build_dataloader: timm's fast_collate + PrefetchLoader).
+
+The reference's loaders hand over uint8 NCHW batches and normalise them on the GPU with mean * 255 / std * 255.  The two classes
+here are that contract on the HIP path: the bytes cross the bus (4x fewer than fp32) and one `vr_normalize_u8` pass -- or, in
+training, the `vr_token_mix_u8` pass of `SwitchTokenMix(input_norm=...)` -- makes the fp32 batch the model reads.
+
+  DevicePrefetchLoader   timm's PrefetchLoader: host batches, copied one batch ahead on a side stream.
+  ResidentU8Batches      a hold-out set kept on the device as uint8 (a quarter of its fp32 size), re-iterable: what
+                         evo_eval.score_candidate / score_population and engine.evaluate take as `batches`.
+
+What is not here: decoding, augmentation and random erasing stay with the loader that produces the uint8 batches.
+"""
+import torch
+
+from . import kernels as K
+
+
+class DevicePrefetchLoader:
+    """Counterpart of timm's PrefetchLoader over a loader of (uint8 NCHW CPU batch, target) pairs: the next batch is copied to
+    `device` on a side stream while the current one is consumed, and every batch is yielded as (normalize_u8(batch), target) on the
+    current stream.  normalize=False yields the uint8 device batch itself -- the training loop's form, where
+    SwitchTokenMix(input_norm=(mean, std)) normalises inside the mix.  mean / std: per-channel, 0..1 units.  Pinned host batches
+    (pin_memory=True) make the copies asynchronous.  __len__, .sampler and .dataset are the wrapped loader's."""
+
+    def __init__(self, loader, device, mean=K.IMAGENET_DEFAULT_MEAN, std=K.IMAGENET_DEFAULT_STD, normalize=True):
+        self.loader, self.device, self.normalize = loader, torch.device(device), normalize
+        self.norm = K.norm_constants(mean, std)
+
+    def __len__(self):
+        return len(self.loader)
+
+    @property
+    def sampler(self):
+        return self.loader.sampler
+
+    @property
+    def dataset(self):
+        return self.loader.dataset
+
+    def _upload(self, side, batch, target):
+        if batch.dtype != torch.uint8:
+            raise TypeError("DevicePrefetchLoader takes uint8 NCHW batches (timm's fast_collate), got %s" % batch.dtype)
+        if side is None:                      # (not a GPU: nothing to overlap; the normaliser itself has no CPU form)
+            return batch.to(self.device), target.to(self.device), None
+        with torch.cuda.stream(side):
+            return batch.to(self.device, non_blocking=True), target.to(self.device, non_blocking=True), side.record_event()
+
+    def __iter__(self):
+        side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
+        ahead = None
+        for batch, target in self.loader:
+            nxt = self._upload(side, batch, target)
+            if ahead is not None:
+                yield self._hand_over(*ahead)
+            ahead = nxt
+        if ahead is not None:
+            yield self._hand_over(*ahead)
+
+    def _hand_over(self, u8, target, copied):
+        if copied is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(copied)
+            u8.record_stream(cur)             # (allocated on the side stream, used on this one)
+            target.record_stream(cur)
+        return (K.normalize_u8(u8, *self.norm) if self.normalize else u8), target
+
+
+class ResidentU8Batches:
+    """A re-iterable over a uint8 image set [N,C,H,W] and its targets [N] that live on the device: yields (fp32 batch, targets)
+    with the batch normalised by vr_normalize_u8 into one of TWO alternating output buffers -- nothing is allocated per batch, the
+    last batch is short when batch_size does not divide N.  A yielded batch is valid until the batch after next is requested (of
+    this or a later iteration): consumers that only launch work on the current stream, as the evaluation loops do, need nothing
+    more.  mean / std: per-channel, 0..1 units."""
+
+    def __init__(self, images_u8, targets, batch_size, mean=K.IMAGENET_DEFAULT_MEAN, std=K.IMAGENET_DEFAULT_STD):
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+            raise TypeError("ResidentU8Batches takes a uint8 [N,C,H,W] tensor, got %s %s" % (images_u8.dtype, tuple(images_u8.shape)))
+        if targets.shape[0] != images_u8.shape[0] or batch_size <= 0:
+            raise ValueError("ResidentU8Batches: one target per image and a positive batch size expected")
+        self.images, self.targets, self.batch_size = images_u8.contiguous(), targets, int(batch_size)
+        self.norm = K.norm_constants(mean, std)
+        n = min(self.batch_size, self.images.shape[0])
+        self._bufs = [torch.empty((n,) + tuple(self.images.shape[1:]), dtype=torch.float32, device=self.images.device)
+                      for _ in range(2)]
+        self._turn = 0
+
+    def __len__(self):
+        return (self.images.shape[0] + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        for lo in range(0, self.images.shape[0], self.batch_size):
+            u8 = self.images[lo:lo + self.batch_size]
+            out = self._bufs[self._turn][:u8.shape[0]]
+            self._turn ^= 1
+            yield K.normalize_u8(u8, *self.norm, out=out), self.targets[lo:lo + self.batch_size]

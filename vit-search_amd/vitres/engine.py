@@ -22,6 +22,7 @@ import torch.distributed as dist
 from . import functional as Fn, kernels as K, stem
 from .losses import SoftTargetCrossEntropy
 from .optim import FlatAdamW, _check_accum_steps
+from .token_mixup import SwitchTokenMix
 
 
 def is_dist():
@@ -680,11 +681,28 @@ class FastPath:
         if p is None or not p.is_cuda:
             raise ValueError("model: fast= needs the model's parameters on the GPU")
 
+    @staticmethod
+    def _key(model, samples_shape, targets_shape, patch_targets_shape, patch_output_type, max_norm, accum_steps, several):
+        return (tuple(samples_shape), tuple(targets_shape), None if patch_targets_shape is None else tuple(patch_targets_shape),
+                patch_output_type, accum_steps, bool(max_norm), model.compute_dtype, several)
+
+    def static_inputs(self, model, samples_shape, targets_shape, patch_targets_shape, patch_output_type, max_norm, accum_steps,
+                      several):
+        """The static (x, t, pt) buffers of the captured step that a batch of these shapes would replay, or None before that step's
+        first capture.  What is written into them on the current stream is what the next replay reads, and the replay then issues no
+        input copy (train_one_epoch mixes straight into them).  Changes nothing: no capture, no reordering of the kept steps."""
+        arena = getattr(model, "_arena", None)
+        key = self._key(model, samples_shape, targets_shape, patch_targets_shape, patch_output_type, max_norm, accum_steps, several)
+        for e in self._entries:
+            if e[0] == key and e[1] is arena and arena is not None:
+                return e[2].x, e[2].t, e[2].pt
+        return None
+
     def _step_for(self, model, criterion, optimizer, samples, targets, patch_targets, patch_output_type, max_norm, accum_steps,
                   several):
         arena = model._ensure_arena(next(model.parameters()).device)
-        key = (tuple(samples.shape), tuple(targets.shape), None if patch_targets is None else tuple(patch_targets.shape),
-               patch_output_type, accum_steps, bool(max_norm), model.compute_dtype, several)
+        key = self._key(model, samples.shape, targets.shape, None if patch_targets is None else patch_targets.shape,
+                        patch_output_type, max_norm, accum_steps, several)
         self._entries = [e for e in self._entries if e[1] is arena]
         optimizer.max_norm = max_norm or None
         optimizer.accum_steps = accum_steps
@@ -768,11 +786,18 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
         patch_targets, patch_output_type = None, None
+        if samples.dtype == torch.uint8 and not getattr(patch_mixup_fn, "normalizes", False):
+            raise TypeError(_U8_MESSAGE % "train_one_epoch")
         if mixup_fn is not None:
             samples, targets = mixup_fn(samples, targets)
             assert patch_mixup_fn is None
         if patch_mixup_fn is not None:
-            samples, targets, patch_targets, patch_output_type = patch_mixup_fn(samples, targets)
+            into = _mix_destination(fast, model, patch_mixup_fn, samples, max_norm, accum_steps, grad_sync)
+            if into is not None:                                  # straight into the captured step's x / t / pt: no copy at replay
+                samples, targets, patch_targets, patch_output_type = patch_mixup_fn(
+                    samples, targets, out=into[0], targets_out=into[1], patch_targets_out=into[2])
+            else:
+                samples, targets, patch_targets, patch_output_type = patch_mixup_fn(samples, targets)
         teacher_output = None
         if teacher_model is not None:
             with torch.no_grad():
@@ -803,6 +828,20 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         m.synchronize_between_processes()
     print_out('Averaged stats: ' + '  '.join('{}: {:.6f}'.format(k, m.global_avg) for k, m in meters.items()))
     return {k: m.global_avg for k, m in meters.items()}
+
+
+_U8_MESSAGE = ("%s got a uint8 image batch: nothing on this path normalises it.  Wrap the loader in "
+               "vitres.data.DevicePrefetchLoader (evaluation), or train with SwitchTokenMix(..., input_norm=(mean, std))")
+
+
+def _mix_destination(fast, model, patch_mixup_fn, samples, max_norm, accum_steps, grad_sync):
+    """Where a vitres SwitchTokenMix writes under fast=: the static inputs of the captured step this batch will replay -- every part of
+    that step's key is known before the mix -- or None (first batch of a key, the eager loop, any other patch_mixup_fn)."""
+    if fast is None or not isinstance(patch_mixup_fn, SwitchTokenMix) or samples.dim() != 4:
+        return None
+    B, pl, nc = samples.shape[0], patch_mixup_fn.patch_len, patch_mixup_fn.num_classes
+    several = grad_sync is not None and grad_sync.world > 1
+    return fast.static_inputs(model, samples.shape, (B, nc), (B, pl * pl, nc), 'seq', max_norm, accum_steps, several)
 
 
 def _full_windows(data_loader, k, print_out=print):

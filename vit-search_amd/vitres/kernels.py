@@ -869,3 +869,37 @@ def patch_fold(col, B, gh, gw, P, C):
     a = torch.empty((B * gh * P * gw * P, C), dtype=col.dtype, device=col.device)
     _lib.check(_lib.lib().vr_patch_unfold(_p(a), _p(col), B, gh, gw, P, C, 1, _dt(col), _stream()), "vr_patch_unfold")
     return a
+
+
+IMAGENET_DEFAULT_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_DEFAULT_STD = (0.229, 0.224, 0.225)
+
+
+def norm_constants(mean, std):
+    """(mean, std) in 0..1 units -> two ctypes float arrays in uint8 units: x * 255 in Python doubles, then rounded to fp32
+    (timm's PrefetchLoader: torch.tensor([x * 255 for x in mean])).  Host memory: the kernels take them by value."""
+    mean, std = [float(m) * 255 for m in mean], [float(s) * 255 for s in std]
+    if len(mean) != len(std) or not 1 <= len(mean) <= 4:
+        raise ValueError("mean and std need one entry per channel, at most 4 (got %d and %d)" % (len(mean), len(std)))
+    arr = ctypes.c_float * len(mean)
+    return arr(*mean), arr(*std)
+
+
+def normalize_u8(u8, mean, std, out=None):
+    """vr_normalize_u8: uint8 [B,C,H,W] -> fp32 (float(u) - mean[c] * 255) / (std[c] * 255), timm's PrefetchLoader statement bit
+    for bit.  mean / std: per-channel sequences in 0..1 units, or the pair norm_constants() made of them; out: a preallocated
+    contiguous fp32 tensor of the same shape."""
+    if u8.dtype != torch.uint8 or u8.dim() != 4:
+        raise TypeError("normalize_u8: a uint8 [B,C,H,W] tensor expected, got %s %s" % (u8.dtype, tuple(u8.shape)))
+    if not isinstance(mean, ctypes.Array):
+        mean, std = norm_constants(mean, std)
+    B, C, H, W = u8.shape
+    if len(mean) != C:
+        raise ValueError("normalize_u8: %d channels but %d normalisation constants" % (C, len(mean)))
+    u8 = u8.contiguous()
+    if out is None:
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=u8.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous():
+        raise ValueError("normalize_u8: out must be a contiguous fp32 tensor of shape %s" % ((B, C, H, W),))
+    _lib.check(_lib.lib().vr_normalize_u8(_p(u8), _p(out), B, C, H, W, mean, std, _stream()), "vr_normalize_u8")
+    return out

@@ -47,6 +47,13 @@ _NUM_WARMUP_EPOCHS = 15
 _REQUIRE_CUDA = True   # tests that emulate the kernels on CPU lift this guard; the kernels themselves never accept CPU tensors
 
 
+def _check_not_u8(x):
+    """uint8 images are a loader's format (timm fast_collate), not the model's: cast to float they would run as 0..255."""
+    if x.dtype == torch.uint8:
+        raise TypeError('the model got a uint8 image batch, which nothing has normalised: wrap the loader in '
+                        'vitres.data.DevicePrefetchLoader, or train with SwitchTokenMix(..., input_norm=(mean, std))')
+
+
 def _cfg(url='', **kwargs):
     return {'url': url, 'num_classes': 1000, 'input_size': (3, 224, 224), 'pool_size': None, 'crop_pct': .9,
             'interpolation': 'bicubic', 'mean': (0.485, 0.456, 0.406), 'std': (0.229, 0.224, 0.225),
@@ -710,6 +717,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
                                '(the CPU restatement lives in oracle/ and is test infrastructure)' % x.device)
         if patch_output_type not in (None, 'seq', 'avg'):
             raise ValueError()
+        _check_not_u8(x)
         self._ensure_arena(x.device)
         # second result of the forward: 0 none, 1 patch head per token ('seq'), 2 patch head on the mean token ('avg'),
         # 3 distillation head (two-token variants, training and eval alike, reference :455-458)
@@ -750,6 +758,7 @@ class FlexibleDistillVisionTransformerSR(nn.Module):
             raise RuntimeError('loss_and_grad is a training-step primitive: call model.train() first')
         if patch_output_type not in (None, 'seq', 'avg'):
             raise ValueError()
+        _check_not_u8(x)
         a = self._ensure_arena(x.device)
         have = any(p_.grad is not None for p_ in a["params"])
         if have and not accumulate:

@@ -5,19 +5,38 @@ permuted partner; the per-patch soft targets follow the box) and the second half
 The random draws use the SAME generators in the SAME order as the reference -- torch's CPU generator for the two
 permutations, numpy's global generator for the Beta samples and the box -- so a run seeded like the reference sees the same
 mixes; the tensor work is one `vr_token_mix` call (two streaming kernels).  Returns the reference's 4-tuple
-`(samples, targets, patch_targets, 'seq')`; unlike the reference the input batch is not modified in place (`out=` lets the
-caller mix straight into e.g. the static input buffer of a captured hipGraph).
+`(samples, targets, patch_targets, 'seq')`; unlike the reference the input batch is not modified in place (`out=`,
+`targets_out=` and `patch_targets_out=` let the caller mix straight into e.g. the static input buffers of a captured hipGraph).
+
+`input_norm=(mean, std)` (0..1 units, e.g. the ImageNet defaults) makes the mix the normaliser of a uint8 input pipeline: the
+batch arrives as uint8 NCHW (timm's fast_collate; `vitres.data.DevicePrefetchLoader(..., normalize=False)`) and one
+`vr_token_mix_u8` pass reads the bytes, normalises as timm's PrefetchLoader does and mixes -- the same bits as normalising first.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .kernels import _p, _stream
+from .kernels import _p, _stream, norm_constants
 
 
 class SwitchTokenMix:
-    def __init__(self, patch_len, switch_prob=0.5, num_classes=1000, smoothing=0.1):
+    def __init__(self, patch_len, switch_prob=0.5, num_classes=1000, smoothing=0.1, input_norm=None):
         self.patch_len, self.switch_prob, self.num_classes, self.smoothing = patch_len, switch_prob, num_classes, smoothing
+        # (mean, std) in uint8 units as two host float arrays, or None: the samples arrive normalised
+        self.input_norm = None if input_norm is None else norm_constants(*input_norm)
+
+    @property
+    def normalizes(self):
+        """True: takes uint8 samples and normalises them (input_norm=); False: takes normalised fp32 samples."""
+        return self.input_norm is not None
+
+    def check_dtype(self, samples):
+        """The dtype rules, before anything is drawn or launched."""
+        if samples.dtype == torch.uint8 and self.input_norm is None:
+            raise ValueError('SwitchTokenMix got uint8 samples but no input_norm=(mean, std): they would be mixed un-normalised')
+        if samples.dtype != torch.uint8 and self.input_norm is not None:
+            raise ValueError('SwitchTokenMix(input_norm=...) normalises uint8 samples; %s samples would be normalised twice'
+                             % samples.dtype)
 
     def __repr__(self):
         return '(patch_len={}, switch_prob={})'.format(self.patch_len, self.switch_prob)
@@ -44,24 +63,35 @@ class SwitchTokenMix:
         return dict(half=h, partner=partner, box=(y0, y0 + int(ch), x0, x0 + int(cw)), lam_patch=float(lam_patch),
                     lam_img=float(lam_img))
 
-    def __call__(self, samples, targets, out=None, draw=None):
+    def __call__(self, samples, targets, out=None, draw=None, targets_out=None, patch_targets_out=None):
+        self.check_dtype(samples)
         if not samples.is_cuda:
             raise RuntimeError('vitres.token_mixup runs on the GPU through libvitres_hip.so (CPU restatement: oracle/)')
         B, C, H, W = samples.shape
         d = draw or self.draw(B)
         K, pl = self.num_classes, self.patch_len
-        x = samples.contiguous().float()
-        out = torch.empty_like(x) if out is None else out
-        new_targets = torch.empty((B, K), dtype=torch.float32, device=x.device)
-        patch_targets = torch.empty((B, pl * pl, K), dtype=torch.float32, device=x.device)
-        partner = d["partner"].to(x.device, non_blocking=True)
-        labels = targets.to(x.device).long().contiguous()
+        x = samples.contiguous() if self.input_norm is not None else samples.contiguous().float()
+        dev = x.device
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if out is None else out
+        new_targets = torch.empty((B, K), dtype=torch.float32, device=dev) if targets_out is None else targets_out
+        patch_targets = torch.empty((B, pl * pl, K), dtype=torch.float32, device=dev) if patch_targets_out is None \
+            else patch_targets_out
+        for name, t, shape in (('out', out, (B, C, H, W)), ('targets_out', new_targets, (B, K)),
+                               ('patch_targets_out', patch_targets, (B, pl * pl, K))):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError('%s must be a contiguous fp32 tensor of shape %s on %s' % (name, shape, dev))
+        partner = d["partner"].to(dev, non_blocking=True)
+        labels = targets.to(dev).long().contiguous()
         off = self.smoothing / K
         on = 1. - self.smoothing + off
         y0, y1, x0, x1 = d["box"]
         f32 = lambda v: float(np.float32(v))                              # noqa: E731  torch rounds python scalars to fp32
-        _lib.check(_lib.lib().vr_token_mix(_p(x), _p(out), _p(labels), _p(partner), _p(new_targets), _p(patch_targets), B, C, H,
-                                           W, K, pl, d["half"], y0, y1, x0, x1, f32(d["lam_patch"]),
-                                           f32(1. - d["lam_patch"]), f32(d["lam_img"]), f32(1. - d["lam_img"]), f32(on),
-                                           f32(off), _stream()), "vr_token_mix")
+        args = (_p(x), _p(out), _p(labels), _p(partner), _p(new_targets), _p(patch_targets), B, C, H, W, K, pl, d["half"], y0, y1,
+                x0, x1, f32(d["lam_patch"]), f32(1. - d["lam_patch"]), f32(d["lam_img"]), f32(1. - d["lam_img"]), f32(on), f32(off))
+        if self.input_norm is not None:
+            if len(self.input_norm[0]) != C:
+                raise ValueError('input_norm has %d channels, the samples %d' % (len(self.input_norm[0]), C))
+            _lib.check(_lib.lib().vr_token_mix_u8(*args, self.input_norm[0], self.input_norm[1], _stream()), "vr_token_mix_u8")
+        else:
+            _lib.check(_lib.lib().vr_token_mix(*args, _stream()), "vr_token_mix")
         return out, new_targets, patch_targets, 'seq'
