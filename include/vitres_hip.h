@@ -447,6 +447,38 @@ int vr_token_mix_u8(const uint8_t* samples, float* out, const int64_t* labels, c
                     vr_stream_t stream);
 
 /*
+ * timm's Mixup / CutMix (timm/data/mixup.py; the reference's `mixup_fn`, main.py:308-314), device half.  Sample i is mixed with
+ * sample j = B-1-i (timm's x.flip(0)) by params[i], a DEVICE array of B entries the host has drawn (vitres/mixup.py: timm's batch,
+ * elem and pair modes all come down to one table):
+ *   cutmix != 0             out[i] = x[j] inside the PIXEL box [y0,y1) x [x0,x1) (aligned to nothing, may be empty), x[i] outside;
+ *                           copies, no arithmetic; the partner is read only by lanes that intersect the box
+ *   cutmix == 0, lam != 1   out[i] = fl(fl(x[i] * lam) + fl(x[j] * oml))      (no FMA; lam and oml rounded by the host)
+ *   cutmix == 0, lam == 1   out[i] = x[i], copied (timm skips these samples; x * 1 + xj * 0 would turn -0.0 into +0.0 and let a
+ *                           non-finite partner through); the partner is not read.  (lam == 1 as timm compares it, on its own
+ *                           double: a lam just below 1 that the host rounded to 1.f comes with oml != 0 and is blended)
+ *   always                  targets[i,c] = fl(fl(y_i(c) * lam) + fl(y_j(c) * oml)), y_s(c) = on_value if c == labels[s] else off_value
+ * samples / out contiguous [B,C,H,W], out != samples; labels int64 [B]; targets fp32 [B,num_classes].
+ * vr_mixup_u8: uint8 samples, bit-identical with vr_normalize_u8 followed by vr_mixup (own / partner chosen on the bytes, the blend
+ *   normalises both); each byte is read once; mean / std and the lane width as vr_normalize_u8.
+ * VR_EINVAL: a null pointer or a non-positive size.  VR_EUNSUPPORTED: W % 4, odd B, samples == out, C > 4 (u8).  VR_EALIGN: samples
+ * (fp32) or out not 16-byte, uint8 samples or params not 4-byte aligned.  Checked before anything is launched.  The boxes live in
+ * device memory: the caller guarantees 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W (vitres.kernels.mixup checks its host copy); a
+ * box outside the image addresses nothing outside the buffers, it only selects pixels.
+ */
+typedef struct vr_mixup_param {
+    float lam, oml;
+    int32_t y0, y1, x0, x1;
+    int32_t cutmix;
+    int32_t pad;
+} vr_mixup_param;   /* 32 bytes */
+
+int vr_mixup(const float* samples, float* out, const int64_t* labels, float* targets, const vr_mixup_param* params, int32_t B,
+             int32_t C, int32_t H, int32_t W, int32_t num_classes, float on_value, float off_value, vr_stream_t stream);
+int vr_mixup_u8(const uint8_t* samples, float* out, const int64_t* labels, float* targets, const vr_mixup_param* params, int32_t B,
+                int32_t C, int32_t H, int32_t W, int32_t num_classes, float on_value, float off_value, const float* mean,
+                const float* std, vr_stream_t stream);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

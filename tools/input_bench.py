@@ -13,7 +13,17 @@ stage; per line the MEDIAN over --iters batches after --warmup.  GB/s = the byte
 draw: a 2 x 2 box of the 4 x 4 grid, so the partner is read for 1/4 of the first half and all of the second) over its time.  Before
 timing, a and b are checked to leave the same bits in x / t / pt.
 
-    python tools/input_bench.py [--iters 60] [--warmup 10] [--out FILE]"""
+    python tools/input_bench.py [--iters 60] [--warmup 10] [--out FILE]
+
+--case mixup: the same question for timm's Mixup / CutMix (vitres.mixup.Mixup, the reference's default mix), B = 128, 3 x 224 x 224,
+K = 1000, batch mode, once for a blend (lam = 0.37) and once for a cutmix (a 112 x 112 box), into a pair of static x / t buffers:
+
+  f   pinned fp32 host batch -> device; vr_mixup into fresh tensors; two copy_ into the static x / t
+  u   pinned uint8 host batch -> device; vr_mixup_u8 straight into the static x / t
+  t   pinned fp32 host batch -> device; timm's torch statements on the device batch (x.flip(0), mul_, add_ / the box assignment,
+      mixup_target on the smoothed one-hots); two copy_ into the static x / t
+
+No model here: the lines alternate back to back.  f and u are checked to leave the same bits; whether t does is reported."""
 import argparse
 import os
 import statistics
@@ -35,9 +45,12 @@ def main():
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default="")
+    ap.add_argument("--case", default="token_mix", choices=["token_mix", "mixup"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("input_bench.py times the GPU path and needs the MI355X")
+    if args.case == "mixup":
+        return mixup_case(args)
     from vitres import engine, kernels as K
     from vitres.losses import SoftTargetCrossEntropy
     from vitres.optim import FlatAdamW
@@ -142,6 +155,118 @@ def main():
         row += " | device %6.1f MB %7.3f ms %7.1f GB/s" % (dev_bytes / 1e6, work, dev_bytes / work / 1e6)
         out.append(row)
     out.append("b / a = %.3f (%s)" % (med["b"] / med["a"], "b is faster" if med["b"] < med["a"] else "b is NOT faster"))
+    text = "\n".join(out)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+def mixup_case(args):
+    from vitres import kernels as K
+    from vitres.mixup import Mixup
+    dev = torch.device("cuda:0")
+    B, S, smoothing = bench.WORKLOADS["sr_tiny_supernet"]["batch"], 224, 0.1
+    mean, std = K.IMAGENET_DEFAULT_MEAN, K.IMAGENET_DEFAULT_STD
+    g = torch.Generator().manual_seed(0)
+    u8_host = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, generator=g)
+    m255 = torch.tensor([x * 255 for x in mean]).view(1, 3, 1, 1)
+    s255 = torch.tensor([x * 255 for x in std]).view(1, 3, 1, 1)
+    f32_host = u8_host.float().sub_(m255).div_(s255).pin_memory()
+    u8_host = u8_host.pin_memory()
+    labels = torch.randint(0, NC, (B,), generator=g).to(dev)
+    box = (40, 152, 70, 182)                                      # 112 x 112 pixels, aligned to no lane
+    draws = {"blend": dict(mode="batch", lam=0.37, cutmix=False, box=None),
+             "cutmix": dict(mode="batch", lam=1. - 112 * 112 / float(S * S), cutmix=True, box=box)}
+    mix_f, mix_u = Mixup(num_classes=NC, label_smoothing=smoothing), Mixup(num_classes=NC, label_smoothing=smoothing,
+                                                                          input_norm=(mean, std))
+    sx, st = torch.empty((B, 3, S, S), device=dev), torch.empty((B, NC), device=dev)
+
+    def one_hot(y, on, off):
+        return torch.full((y.size(0), NC), off, device=dev).scatter_(1, y.long().view(-1, 1), on)
+
+    def timm_statements(x, y, d):                                 # timm 0.3.2 Mixup._mix_batch + mixup_target, on the device
+        lam = d["lam"]
+        if d["box"] is not None:
+            yl, yh, xl, xh = d["box"]
+            x[:, :, yl:yh, xl:xh] = x.flip(0)[:, :, yl:yh, xl:xh]
+        elif lam != 1.:
+            x_flipped = x.flip(0).mul_(1. - lam)
+            x.mul_(lam).add_(x_flipped)
+        off = smoothing / NC
+        on = 1. - smoothing + off
+        return x, one_hot(y, on, off) * lam + one_hot(y.flip(0), on, off) * (1. - lam)
+
+    def stage_f(ev, d):
+        ev[0].record()
+        s = f32_host.to(dev, non_blocking=True)
+        ev[1].record()
+        x, t = mix_f(s, labels, draw=d)
+        sx.copy_(x, non_blocking=True)
+        st.copy_(t, non_blocking=True)
+        ev[2].record()
+
+    def stage_u(ev, d):
+        ev[0].record()
+        s = u8_host.to(dev, non_blocking=True)
+        ev[1].record()
+        mix_u(s, labels, draw=d, out=sx, targets_out=st)
+        ev[2].record()
+
+    def stage_t(ev, d):
+        ev[0].record()
+        s = f32_host.to(dev, non_blocking=True)
+        ev[1].record()
+        x, t = timm_statements(s, labels, d)
+        sx.copy_(x, non_blocking=True)
+        st.copy_(t, non_blocking=True)
+        ev[2].record()
+
+    N = B * 3 * S * S
+    T = 4 * B * NC
+    stages = (("f fp32 H2D + vr_mixup + 2 copy_", stage_f, 4 * N), ("u uint8 H2D + vr_mixup_u8 in place", stage_u, N),
+              ("t fp32 H2D + timm's torch statements + 2 copy_", stage_t, 4 * N))
+    same_t = {}
+    for dn, d in draws.items():                                   # the bits, before any timing
+        got = []
+        for _, fn, _ in stages:
+            sx.zero_(), st.zero_()
+            fn([torch.cuda.Event(enable_timing=True) for _ in range(3)], d)
+            got.append((sx.clone(), st.clone()))
+        if not (torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])):
+            sys.exit("input_bench.py: vr_mixup_u8 does not reproduce vr_mixup's bits (%s)" % dn)
+        same_t[dn] = torch.equal(got[0][0], got[2][0]) and torch.equal(got[0][1], got[2][1])
+    # the bytes each of OUR lines must move on the device (the partner is read for the whole batch in a blend, for the box in a cutmix)
+    partner = {"blend": 1., "cutmix": 112 * 112 / float(S * S)}
+    times = {(name, dn): ([], []) for name, _, _ in stages for dn in draws}
+    for i in range(args.warmup + args.iters):
+        for dn, d in draws.items():
+            for name, fn, _ in stages:
+                evs = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                fn(evs, d)
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    times[(name, dn)][0].append(evs[0].elapsed_time(evs[1]))
+                    times[(name, dn)][1].append(evs[1].elapsed_time(evs[2]))
+    out = ["Mixup / CutMix input stage per batch: B = %d, 3 x %d x %d, K = %d, batch mode, into static x / t; median of %d after %d "
+           "warm-up, HIP events, lines alternating back to back (no model step between them); x / t of f and u bit-identical"
+           % (B, S, S, NC, args.iters, args.warmup)]
+    for dn in draws:
+        out.append("%s (%s): timm's torch statements on the device leave %s bits as vr_mixup" % (
+            dn, "lam = 0.37" if dn == "blend" else "box %s" % (box,), "the same" if same_t[dn] else "NOT the same"))
+        for name, _, host_bytes in stages:
+            h2d, work = statistics.median(times[(name, dn)][0]), statistics.median(times[(name, dn)][1])
+            tot = [p + q for p, q in zip(*times[(name, dn)])]
+            row = "  %-48s total %7.3f ms (min %.3f max %.3f) | H2D %6.1f MB %7.3f ms %6.1f GB/s | device %7.3f ms" % (
+                name, statistics.median(tot), min(tot), max(tot), host_bytes / 1e6, h2d, host_bytes / h2d / 1e6, work)
+            if name[0] == "f":
+                dev_bytes = (1 + partner[dn]) * 4 * N + 4 * N + T + 2 * (4 * N + T)
+                row += " %6.1f MB %7.1f GB/s" % (dev_bytes / 1e6, dev_bytes / work / 1e6)
+            elif name[0] == "u":
+                dev_bytes = (1 + partner[dn]) * N + 4 * N + T
+                row += " %6.1f MB %7.1f GB/s" % (dev_bytes / 1e6, dev_bytes / work / 1e6)
+            out.append(row)
     text = "\n".join(out)
     print(text)
     if args.out:

@@ -52,6 +52,11 @@ class LnGradSlot(ctypes.Structure):
                 ("reserved", c_int32)]
 
 
+class MixupParam(ctypes.Structure):
+    _fields_ = [("lam", c_float), ("oml", c_float), ("y0", c_int32), ("y1", c_int32), ("x0", c_int32), ("x1", c_int32),
+                ("cutmix", c_int32), ("pad", c_int32)]
+
+
 # name -> argtypes ; every entry point returns int.  Must list every symbol of include/vitres_hip.h
 SYMBOLS = {
     "vr_version": [],
@@ -92,6 +97,8 @@ SYMBOLS = {
     "vr_token_mix": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p],
     "vr_normalize_u8": [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p, c_void_p],
     "vr_token_mix_u8": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p, c_void_p, c_void_p],
+    "vr_mixup": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p],
+    "vr_mixup_u8": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p, c_void_p, c_void_p],
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],

@@ -21,6 +21,7 @@ import torch.distributed as dist
 
 from . import functional as Fn, kernels as K, stem
 from .losses import SoftTargetCrossEntropy
+from .mixup import Mixup
 from .optim import FlatAdamW, _check_accum_steps
 from .token_mixup import SwitchTokenMix
 
@@ -786,10 +787,15 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
         samples = samples.to(device, non_blocking=True)
         targets = targets.to(device, non_blocking=True)
         patch_targets, patch_output_type = None, None
-        if samples.dtype == torch.uint8 and not getattr(patch_mixup_fn, "normalizes", False):
+        if samples.dtype == torch.uint8 and not (getattr(patch_mixup_fn, "normalizes", False)
+                                                 or getattr(mixup_fn, "normalizes", False)):
             raise TypeError(_U8_MESSAGE % "train_one_epoch")
         if mixup_fn is not None:
-            samples, targets = mixup_fn(samples, targets)
+            into = _mix_destination(fast, model, mixup_fn, samples, max_norm, accum_steps, grad_sync)
+            if into is not None:                                  # straight into the captured step's x / t: no copy at replay
+                samples, targets = mixup_fn(samples, targets, out=into[0], targets_out=into[1])
+            else:
+                samples, targets = mixup_fn(samples, targets)
             assert patch_mixup_fn is None
         if patch_mixup_fn is not None:
             into = _mix_destination(fast, model, patch_mixup_fn, samples, max_norm, accum_steps, grad_sync)
@@ -831,17 +837,25 @@ def train_one_epoch(model, criterion, data_loader, optimizer, device, epoch, los
 
 
 _U8_MESSAGE = ("%s got a uint8 image batch: nothing on this path normalises it.  Wrap the loader in "
-               "vitres.data.DevicePrefetchLoader (evaluation), or train with SwitchTokenMix(..., input_norm=(mean, std))")
+               "vitres.data.DevicePrefetchLoader (evaluation), or train with SwitchTokenMix(..., input_norm=(mean, std)) "
+               "or Mixup(..., input_norm=(mean, std))")
 
 
-def _mix_destination(fast, model, patch_mixup_fn, samples, max_norm, accum_steps, grad_sync):
-    """Where a vitres SwitchTokenMix writes under fast=: the static inputs of the captured step this batch will replay -- every part of
-    that step's key is known before the mix -- or None (first batch of a key, the eager loop, any other patch_mixup_fn)."""
-    if fast is None or not isinstance(patch_mixup_fn, SwitchTokenMix) or samples.dim() != 4:
+def _mix_destination(fast, model, mix, samples, max_norm, accum_steps, grad_sync):
+    """Where a vitres SwitchTokenMix (x, t, pt) or Mixup (x, t; no patch targets) writes under fast=: the static inputs of the captured
+    step this batch will replay -- every part of that step's key is known before the mix -- or None (first batch of a key, the eager
+    loop, any other mix)."""
+    if fast is None or samples.dim() != 4:
         return None
-    B, pl, nc = samples.shape[0], patch_mixup_fn.patch_len, patch_mixup_fn.num_classes
+    B = samples.shape[0]
+    if isinstance(mix, SwitchTokenMix):
+        pt_shape, pot = (B, mix.patch_len * mix.patch_len, mix.num_classes), 'seq'
+    elif isinstance(mix, Mixup):
+        pt_shape, pot = None, None
+    else:
+        return None
     several = grad_sync is not None and grad_sync.world > 1
-    return fast.static_inputs(model, samples.shape, (B, nc), (B, pl * pl, nc), 'seq', max_norm, accum_steps, several)
+    return fast.static_inputs(model, samples.shape, (B, mix.num_classes), pt_shape, pot, max_norm, accum_steps, several)
 
 
 def _full_windows(data_loader, k, print_out=print):

@@ -6,6 +6,7 @@ for device memory and streams only.  Non-CUDA tensors raise: there is no CPU pat
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -903,3 +904,57 @@ def normalize_u8(u8, mean, std, out=None):
         raise ValueError("normalize_u8: out must be a contiguous fp32 tensor of shape %s" % ((B, C, H, W),))
     _lib.check(_lib.lib().vr_normalize_u8(_p(u8), _p(out), B, C, H, W, mean, std, _stream()), "vr_normalize_u8")
     return out
+
+
+# one row of the device table of vr_mixup / vr_mixup_u8 (vr_mixup_param of include/vitres_hip.h, 32 bytes)
+MIXUP_PARAM = np.dtype([("lam", "<f4"), ("oml", "<f4"), ("y0", "<i4"), ("y1", "<i4"), ("x0", "<i4"), ("x1", "<i4"),
+                        ("cutmix", "<i4"), ("pad", "<i4")])
+assert MIXUP_PARAM.itemsize == ctypes.sizeof(_lib.MixupParam) == 32
+
+
+def check_mixup_params(params, B, H, W, what="vr_mixup"):
+    """params as a contiguous MIXUP_PARAM array of B rows whose boxes lie inside H x W (an empty box is legal); the device kernel
+    cannot report a bad row, so the host copy is what is checked: RuntimeError VR_EINVAL, before anything is launched."""
+    params = np.ascontiguousarray(params, dtype=MIXUP_PARAM)
+    if params.shape != (B,):
+        raise ValueError("%s: the parameter table has shape %s, the batch %d samples" % (what, params.shape, B))
+    bad = ((params["y0"] < 0) | (params["y0"] > params["y1"]) | (params["y1"] > H)
+           | (params["x0"] < 0) | (params["x0"] > params["x1"]) | (params["x1"] > W))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise RuntimeError("%s failed: %s: the box [%d,%d) x [%d,%d) of sample %d is not inside the %d x %d image" % (
+            what, _lib._ERR[-1], params["y0"][i], params["y1"][i], params["x0"][i], params["x1"][i], i, H, W))
+    return params
+
+
+def mixup(x, labels, params, num_classes, on, off, norm=None, out=None, targets_out=None):
+    """vr_mixup (fp32 x) / vr_mixup_u8 (uint8 x, norm = the pair norm_constants() made): timm's Mixup / CutMix of sample i with
+    sample B-1-i by row i of `params` (a MIXUP_PARAM array: lam and 1 - lam already rounded to fp32 by the rule of the mode that drew
+    them, a pixel box, the cutmix flag) and the mixed smoothed one-hot targets of the int64 `labels`; on / off: the one-hot values.
+    The table is built in pinned host memory and uploaded on the current stream without a host wait.  Returns (out, targets):
+    fresh fp32 tensors, or the contiguous fp32 out= [B,C,H,W] / targets_out= [B,num_classes] written in place; x is not modified."""
+    what = "vr_mixup" if norm is None else "vr_mixup_u8"
+    want = torch.float32 if norm is None else torch.uint8
+    if x.dim() != 4 or x.dtype != want:
+        raise TypeError("%s: a %s [B,C,H,W] tensor expected, got %s %s" % (what, want, x.dtype, tuple(x.shape)))
+    B, C, H, W = x.shape
+    params = check_mixup_params(params, B, H, W, what)
+    if norm is not None and len(norm[0]) != C:
+        raise ValueError("%s: %d channels but %d normalisation constants" % (what, C, len(norm[0])))
+    _p(x)                                                          # (a CPU tensor is refused before anything is allocated)
+    x, dev = x.contiguous(), x.device
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if out is None else out
+    targets = torch.empty((B, num_classes), dtype=torch.float32, device=dev) if targets_out is None else targets_out
+    for name, t, shape in (("out", out, (B, C, H, W)), ("targets_out", targets, (B, num_classes))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s: %s must be a contiguous fp32 tensor of shape %s on %s" % (what, name, shape, dev))
+    host = torch.empty((B, MIXUP_PARAM.itemsize // 4), dtype=torch.int32, pin_memory=True)
+    host.numpy()[:] = params.view(np.int32).reshape(B, -1)
+    table = host.to(dev, non_blocking=True)
+    labels = labels.to(dev).long().contiguous()
+    args = (_p(x), _p(out), _p(labels), _p(targets), _p(table), B, C, H, W, num_classes, float(np.float32(on)), float(np.float32(off)))
+    if norm is None:
+        _lib.check(_lib.lib().vr_mixup(*args, _stream()), what)
+    else:
+        _lib.check(_lib.lib().vr_mixup_u8(*args, norm[0], norm[1], _stream()), what)
+    return out, targets
