@@ -121,12 +121,14 @@ def ln_fwd(x, w, b, keep, rows_per_sample, eps, out_dtype):
     M = X.shape[0]
     mask, kc = _keep_mask(keep, M, C, rows_per_sample)
     Xm = X * mask
-    mu = Xm.sum(1) / kc
+    inv_n = torch.where(kc > 0, 1.0 / kc.clamp(min=1), torch.zeros_like(kc))       # a row with keep = 0: mean 0, rstd eps^-1/2, y 0
+    mu = Xm.sum(1) * inv_n
     if keep is None:
         var = ((X - mu[:, None]) ** 2).mean(1)
     else:
-        var = (Xm * Xm).sum(1) / kc - mu * mu
-    rstd = 1.0 / torch.sqrt(var + eps)
+        var = (Xm * Xm).sum(1) * inv_n - mu * mu
+    # clamped at 0 as in the kernels: the masked form goes negative in fp32 on a row whose mean is large against its spread (a NaN rstd)
+    rstd = 1.0 / torch.sqrt(var.clamp(min=0) + eps)
     y = (w * ((Xm - mu[:, None]) * rstd[:, None]) + b) * mask
     return y.view(x.shape).to(out_dtype), mu, rstd
 
@@ -140,8 +142,9 @@ def ln_bwd(dy, x, w, mean, rstd, keep, rows_per_sample, dx_in, dw, db, next_cast
     G = G * mask
     z = (X - mean[:, None]) * rstd[:, None] * mask
     dz = G * w
-    s1 = dz.sum(1) / kc
-    s2 = (dz * z).sum(1) / kc
+    inv_n = torch.where(kc > 0, 1.0 / kc.clamp(min=1), torch.zeros_like(kc))       # keep = 0: s1 = s2 = 0 and dx = 0, as the kernel defines
+    s1 = dz.sum(1) * inv_n
+    s2 = (dz * z).sum(1) * inv_n
     dx = (dz - (s1[:, None] + z * s2[:, None])) * rstd[:, None]
     if dx_in is not None:
         dx = dx + dx_in.reshape(-1, C)

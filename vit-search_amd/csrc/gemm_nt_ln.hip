@@ -314,7 +314,9 @@ __global__ __launch_bounds__(NTHR, NJ > 5 ? 2 : 3) void ntln_kernel(   // (32 x 
                         }
                         var = wave_sum(d2) * inv_n;
                     }
-                    const float rs = 1.0f / sqrtf(var + f.eps);
+                    // (variance clamped at 0: in fp32 the masked form E[x^2]/p - mu^2 goes negative on a row whose mean is large against its spread,
+                    // and var + eps < 0 is a NaN rstd; the reference yields that NaN, or an rstd above eps^-1/2 -- only there do we depart from it)
+                    const float rs = 1.0f / sqrtf((var < 0.f ? 0.f : var) + f.eps);       // (not fmaxf: a NaN var stays NaN)
                     if (rok) {
                         if (lane == 0) { f.mean[rm[u].orow] = mu; f.rstd[rm[u].orow] = rs; }
 #pragma unroll

@@ -133,7 +133,9 @@ __device__ __forceinline__ void lnf_rows(const vr_gemm_args& p, const vr_ln_epil
                 }
                 var = wave_sum(d2) * inv_n;
             }
-            const float rs = 1.0f / sqrtf(var + ln.eps);
+            // (variance clamped at 0: in fp32 the masked form E[x^2]/p - mu^2 goes negative on a row whose mean is large against its spread,
+            // and var + eps < 0 is a NaN rstd; the reference yields that NaN, or an rstd above eps^-1/2 -- only there do we depart from it)
+            const float rs = 1.0f / sqrtf((var < 0.f ? 0.f : var) + ln.eps);       // (not fmaxf: a NaN var stays NaN)
             if (lane == 0) {
                 ln.mean[m] = mu;
                 ln.rstd[m] = rs;

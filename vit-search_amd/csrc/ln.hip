@@ -81,7 +81,9 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
             }
             var = wave_sum(d2) * inv_n;
         }
-        const float rs = 1.0f / sqrtf(var + eps);
+        // (variance clamped at 0: in fp32 the masked form E[x^2]/p - mu^2 goes negative on a row whose mean is large against its spread,
+        // and var + eps < 0 is a NaN rstd; the reference yields that NaN, or an rstd above eps^-1/2 -- only there do we depart from it)
+        const float rs = 1.0f / sqrtf((var < 0.f ? 0.f : var) + eps);       // (not fmaxf: a NaN var stays NaN)
         if (lane == 0) {
             mean[m] = mu;
             rstd[m] = rs;
