@@ -1,5 +1,6 @@
 """Unit parity of every HIP kernel (through the C ABI) against the torch statement of its semantics
-(tests/emu_kernels.py) on seeded inputs.  fp32 kernels: ~1e-5; bf16 kernels: bf16 rounding of the outputs."""
+(tests/emu_kernels.py) on seeded inputs.  fp32 kernels: ~1e-5; bf16 kernels: bf16 rounding of the outputs.
+Per-element derived bounds live in the three ref64 suites: attn_ref64 / test_gpu_attention, rowstat_ref64 / test_gpu_rowstat, stem_ref64 / test_gpu_stem."""
 import numpy as np
 import pytest
 import torch

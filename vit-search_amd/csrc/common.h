@@ -127,6 +127,10 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// ReLU that keeps NaN (fmaxf(NaN, 0) = 0 would turn a broken activation into a sound-looking zero): NaN fails `v <= 0` and passes
+// through, -0 and negatives give +0 (torch.relu's values)
+__device__ __forceinline__ float relu_f(float v) { return v <= 0.f ? 0.f : v; }
+
 // exact (erf) GELU and its derivative, as nn.GELU() default (reference nets/supernet_blocks.py:18)
 __device__ __forceinline__ float gelu_f(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752f)); }
 __device__ __forceinline__ float dgelu_f(float u) {

@@ -98,8 +98,8 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(const bf16_t* __restrict__
                     f32x4 r4 = nt == 0 ? acc0 : acc1;
                     if (bias) {      // evaluation: BatchNorm folded into the weights, out = relu(conv + shift) (+ residual)
                         const float4 bb = *reinterpret_cast<const float4*>(bias + co);
-                        r4[0] = fmaxf(r4[0] + bb.x, 0.f); r4[1] = fmaxf(r4[1] + bb.y, 0.f);
-                        r4[2] = fmaxf(r4[2] + bb.z, 0.f); r4[3] = fmaxf(r4[3] + bb.w, 0.f);
+                        r4[0] = relu_f(r4[0] + bb.x); r4[1] = relu_f(r4[1] + bb.y);
+                        r4[2] = relu_f(r4[2] + bb.z); r4[3] = relu_f(r4[3] + bb.w);
                     }
                     if (res) {       // residual (evaluation: behind the ReLU; data gradients: the gradient of the stem's skip branch)
                         long long rpix = ((long long)b * H + oy) * W + ox;         // rpsz > 0: the residual is stored in patch order
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256) void conv1_direct_kernel(const float* __restri
                             const float4 bb = *reinterpret_cast<const float4*>(bias + co);
                             r4[0] += bb.x; r4[1] += bb.y; r4[2] += bb.z; r4[3] += bb.w;
                         }
-                        if (relu) { r4[0] = fmaxf(r4[0], 0.f); r4[1] = fmaxf(r4[1], 0.f); r4[2] = fmaxf(r4[2], 0.f); r4[3] = fmaxf(r4[3], 0.f); }
+                        if (relu) { r4[0] = relu_f(r4[0]); r4[1] = relu_f(r4[1]); r4[2] = relu_f(r4[2]); r4[3] = relu_f(r4[3]); }
                         if constexpr (sizeof(TO) == 4) *reinterpret_cast<float4*>(dst + co) = make_float4(r4[0], r4[1], r4[2], r4[3]);
                         else *reinterpret_cast<uint2*>(dst + co) = make_uint2(Half16<TO>::pk(r4[0], r4[1]), Half16<TO>::pk(r4[2], r4[3]));
                     }

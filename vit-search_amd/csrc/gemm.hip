@@ -394,7 +394,7 @@ __device__ __forceinline__ void epilogue_all(const vr_gemm_args& p, f32x16 (&acc
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         v[e] = kc[e] ? v[e] : 0.f;       // masked hidden units: u = 0, gelu(u) = 0 (their K loop may be skipped)
-                        h[e] = kc[e] ? (p.act == 3 ? fmaxf(v[e], 0.f) : (sizeof(T) == 2 ? gelu_fast(v[e]) : gelu_f(v[e]))) : 0.f;
+                        h[e] = kc[e] ? (p.act == 3 ? relu_f(v[e]) : (sizeof(T) == 2 ? gelu_fast(v[e]) : gelu_f(v[e]))) : 0.f;
                         if (p.act == 2) v[e] = kc[e] ? (sizeof(T) == 2 ? dgelu_fast(v[e]) : dgelu_f(v[e])) : 0.f;   // C = gelu'(u)
                     }
                     if (any) {
@@ -506,7 +506,7 @@ __device__ __forceinline__ void epilogue_lds(const vr_gemm_args& p, f32x16 (&acc
 #pragma unroll
                 for (int e = 0; e < CW; ++e) {
                     v[e] = kc[e] ? v[e] : 0.f;       // masked hidden units: u = 0, gelu(u) = 0 (their K loop may be skipped)
-                    h[e] = kc[e] ? (p.act == 3 ? fmaxf(v[e], 0.f) : (sizeof(T) == 2 ? gelu_fast(v[e]) : gelu_f(v[e]))) : 0.f;
+                    h[e] = kc[e] ? (p.act == 3 ? relu_f(v[e]) : (sizeof(T) == 2 ? gelu_fast(v[e]) : gelu_f(v[e]))) : 0.f;
                     if (p.act == 2) v[e] = kc[e] ? (sizeof(T) == 2 ? dgelu_fast(v[e]) : dgelu_f(v[e])) : 0.f;   // C = gelu'(u)
                 }
                 if (any) {

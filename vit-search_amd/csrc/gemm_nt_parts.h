@@ -231,7 +231,7 @@ __device__ __forceinline__ void epilogue(const vr_gemm_args& p, f32x4 (&acc)[MI]
                     }
                 } else if (p.act == 3) {                           // ReLU (BatchNorm-folded convolutions of the evaluation stem)
 #pragma unroll
-                    for (int e = 0; e < CW; ++e) hh[e] = fmaxf(v[e], 0.f);
+                    for (int e = 0; e < CW; ++e) hh[e] = relu_f(v[e]);
                 } else {
 #pragma unroll
                     for (int e = 0; e < CW; ++e) hh[e] = gelu_fast(v[e]);

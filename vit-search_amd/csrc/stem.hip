@@ -212,7 +212,7 @@ __global__ __launch_bounds__(256) void bn_relu_kernel(const TZ* __restrict__ z, 
         if (res) V8<T>::load(res + i * 8, r);
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float v = fmaxf(f[e] * scale[c0 + e] + shift[c0 + e], 0.f);
+            float v = relu_f(f[e] * scale[c0 + e] + shift[c0 + e]);
             if (res) v += r[e];
             f[e] = v;
         }
@@ -438,7 +438,8 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sum, const float* _
     if (c == 0 && nbt) *nbt += 1;
     if (c >= C) return;
     const float mu = sum[c] / n;
-    const float var = fmaxf(sumsq[c] / n - mu * mu, 0.f);
+    const float v0 = sumsq[c] / n - mu * mu;
+    const float var = v0 < 0.f ? 0.f : v0;                              // (not fmaxf: a NaN var stays NaN)
     if (rmean) {
         rmean[c] = rmean[c] * (1.0f - momentum) + momentum * mu;
         rvar[c] = rvar[c] * (1.0f - momentum) + momentum * (var * (n / fmaxf(n - 1.0f, 1.0f)));
