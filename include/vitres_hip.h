@@ -68,7 +68,8 @@ typedef struct vr_rowmap {
  * rows m of sample s and (k % k_period) >= keep_k[s]; K slices with no kept k for any sample of the tile are not
  * loaded, and output tiles with no kept column (keep_n) skip their whole K loop (they still store the masked value).
  * In wgrad form the samples are those of the token range of the split: keep_k bounds the kept output ROWS, keep_n the
- * kept output COLUMNS (rows/columns beyond are exactly zero gradients); fully masked tiles are not computed.
+ * kept output COLUMNS (rows/columns beyond are exactly zero gradients); fully masked tiles are not computed -- except the tile that
+ * owns bias_grad, which runs whenever a row is kept: the bias gradient sums A over all tokens, whatever columns B keeps.
  */
 typedef struct vr_gemm_args {
     const void* A;
@@ -84,7 +85,8 @@ typedef struct vr_gemm_args {
     const void* dact_u;  /* pre-activation for gelu' (dtype = in_dtype, leading dim ldu) or NULL */
     const int32_t* keep_k; /* [batch] or NULL: work-skipping hint, see below */
     float* bias_grad;    /* wgrad only (a_trans && atomic): bias_grad[m] += sum_k A[k][m]  (the Linear's bias gradient,
-                            fused so that dY is read once), or NULL */
+                            fused so that dY is read once), or NULL.  The sum runs over ALL tokens: keep_n (the kept columns of X)
+                            does not bound it -- a sample whose input width is 0 still has a bias gradient */
     int32_t M, N, K;
     int32_t lda, ldb, ldc, ldu;
     int32_t a_trans, b_trans;

@@ -1,6 +1,7 @@
 """Unit parity of every HIP kernel (through the C ABI) against the torch statement of its semantics
 (tests/emu_kernels.py) on seeded inputs.  fp32 kernels: ~1e-5; bf16 kernels: bf16 rounding of the outputs.
-Per-element derived bounds live in the three ref64 suites: attn_ref64 / test_gpu_attention, rowstat_ref64 / test_gpu_rowstat, stem_ref64 / test_gpu_stem."""
+Per-element derived bounds live in the four ref64 suites: attn_ref64 / test_gpu_attention, rowstat_ref64 / test_gpu_rowstat, stem_ref64 / test_gpu_stem,
+gemm_ref64 / test_gpu_gemm."""
 import numpy as np
 import pytest
 import torch
@@ -29,7 +30,8 @@ def tol(dtype):
 def tol32(dtype):
     """fp32 OUTPUT of a GEMM: with bf16 operands the emulation multiplies the same bf16-rounded values and accumulates in fp32
     like the MFMAs do -- only the summation order differs.  (1.2e-2 is for bf16 OUTPUTS: one ulp of the largest value; at that
-    width a wrong fragment in one of 80 K slices would pass.)"""
+    width a wrong fragment in one of 80 K slices would pass HERE -- tests/test_gpu_gemm.py closes that hole: per-element bounds against
+    a float64 contract, where a skipped or repeated slice of one tile misses by four orders of magnitude, and bit-exact probes.)"""
     return 2e-5 if dtype == torch.float32 else 1e-4
 
 

@@ -587,8 +587,10 @@ __global__ __launch_bounds__(TC::NTHR, 2) void gemm_kernel(const vr_gemm_args p)
             const int nmax = max_keep(p.keep_n, s_lo, s_hi, 1 << 30);
             n_any = range_has_kept(n0, BN, p.n_period, nmax);
             if constexpr (TA) {
-                // wgrad: keep_k bounds the kept output rows; a tile without kept rows or columns adds exactly zero
-                if (!n_any || !range_has_kept(m0, BM, p.k_period, kmax)) ntiles = 0;
+                // wgrad: keep_k bounds the kept output rows; a tile without kept rows or columns adds exactly zero -- but the tile
+                // that owns the bias gradient (a sum of A over ALL tokens, whatever B keeps) runs whenever a row is kept
+                const bool bg_tile = p.bias_grad != nullptr && tn == 0;
+                if ((!n_any && !bg_tile) || !range_has_kept(m0, BM, p.k_period, kmax)) ntiles = 0;
             }
         }
         la.init(reinterpret_cast<const T*>(p.A), p.lda, amap, m0, p.M, t);

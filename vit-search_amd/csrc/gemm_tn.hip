@@ -118,7 +118,10 @@ __device__ __forceinline__ void tn_body(const vr_gemm_args& p, const int bid) {
         if (p.rows_in > 0) { s_lo = kbeg / p.rows_in; s_hi = (kend - 1) / p.rows_in; }
         kmax = max_keep(p.keep_k, s_lo, s_hi, 1 << 30);
         nmax = max_keep(p.keep_n, s_lo, s_hi, 1 << 30);
-        if (!range_has_kept(n0, TW, p.n_period, nmax) || !range_has_kept(m0, TW, p.k_period, kmax)) ntiles = 0;
+        // (the bias gradient sums dY over ALL tokens, whatever X keeps: the tile that owns it runs its loop whenever a row is kept --
+        // its X chunks read as zeros, its columns stay unwritten -- or the tokens of samples with keep_n = 0 would be missing from it)
+        const bool bg_tile = BIAS && p.bias_grad != nullptr && tn == 0;
+        if ((!bg_tile && !range_has_kept(n0, TW, p.n_period, nmax)) || !range_has_kept(m0, TW, p.k_period, kmax)) ntiles = 0;
     }
     // atomic == 2 (store form, split_k == 1): the tile's one workgroup OVERWRITES the gradient -- no zero-filled destination, no
     // read-modify-write; a fully masked tile must then write its zeros instead of leaving
@@ -379,7 +382,8 @@ __device__ __forceinline__ void tn8_body(const vr_gemm_args& p, const int bid, c
         if (p.rows_in > 0) { s_lo = kbeg / p.rows_in; s_hi = (kend - 1) / p.rows_in; }
         kmax = max_keep(p.keep_k, s_lo, s_hi, 1 << 30);
         nmax = max_keep(p.keep_n, s_lo, s_hi, 1 << 30);
-        if (!range_has_kept(n0, TW, p.n_period, nmax) || !range_has_kept(m0, TW, p.k_period, kmax)) ntiles = 0;
+        const bool bg_tile = p.bias_grad != nullptr && tn == 0;       // (as in tn_body: the bias gradient's tile ignores keep_n)
+        if ((!bg_tile && !range_has_kept(n0, TW, p.n_period, nmax)) || !range_has_kept(m0, TW, p.k_period, kmax)) ntiles = 0;
     }
     if (ntiles == 0) return;
     const bool skipm = !p.keep_k || (p.k_period > 0 && (p.k_period & 7)), skipn = !p.keep_n || (p.n_period > 0 && (p.n_period & 7));
