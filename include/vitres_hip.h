@@ -481,6 +481,64 @@ int vr_mixup_u8(const uint8_t* samples, float* out, const int64_t* labels, float
                 const float* std, vr_stream_t stream);
 
 /*
+ * timm's RandomErasing (timm/data/random_erasing.py; the reference's --reprob 0.25 --remode pixel --recount 1, applied per sample
+ * to the NORMALISED image before collation and therefore before any mix), device half.  The host draws the rectangles
+ * (vitres/random_erasing.py: timm's order on Python's `random`); the device fills them.
+ *   rects   a DEVICE table [B][R] of vr_erase_rect, 1 <= R <= 4: sample b erases the pixels [y0,y1) x [x0,x1) of every channel for
+ *           each of its R rectangles.  y0 == y1 is the empty rectangle.  Where rectangles overlap the LATER one wins (this shows
+ *           only in 'rand').  The caller guarantees 0 <= y0 <= y1 <= H and 0 <= x0 <= x1 <= W (vitres.kernels checks its host
+ *           copy); the kernels only ever COMPARE pixel coordinates with a rectangle, so one outside the image selects pixels
+ *           and addresses nothing outside the buffers.
+ *   mode    VR_ERASE_CONST: +0.0.  VR_ERASE_RAND: one N(0,1) value per channel per rectangle.  VR_ERASE_PIXEL: N(0,1) per element.
+ * The noise contract -- the value at a pixel is a pure function of (seed, call, b, c, y, x, mode, and the rectangle index for
+ * 'rand'); it does not depend on the lane width, the grid, pointer alignment or the entry point that produced it:
+ *   (r0, r1, r2, r3) = Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85),
+ *       key     = (seed & 0xffffffff, seed >> 32)
+ *       counter = (w, b + (domain << 24), call & 0xffffffff, call >> 32)          b < 2^24
+ *       domain 0 ('pixel'): w = q = ((c * H + y) * W + x) / 4, the index of the aligned 4-pixel quad within the sample
+ *       domain 1 ('rand'):  w = the rectangle's index in the sample's row of the table
+ *   two Box-Muller pairs, (r0, r1) -> (z0, z1) and (r2, r3) -> (z2, z3), in fp32:
+ *       u1 = ((r >> 8) + 1) * 2^-24   in (0, 1]        u2 = (r' >> 8) * 2^-24   in [0, 1)          (both exact)
+ *       rad = sqrtf(-2 * logf(u1))    ang = fl(0x1.921fb6p+2f * u2)    z = fl(rad * cosf(ang)),  z' = fl(rad * sinf(ang))
+ *     with the accurate device functions (no fast-math forms), every product rounded on its own.  |z| <= sqrt(48 ln 2) < 5.77.
+ *   domain 0: z0..z3 are pixels x .. x+3 of the quad.  domain 1: z0..z3 are the colours of channels 0..3.
+ *   `call` is a 64-bit counter the host advances once per batch; `seed` names the stream.
+ * vr_random_erase: in place on a normalised fp32 batch [B,C,H,W]; only quads that meet a rectangle are read or written.
+ * vr_normalize_u8_erase, vr_token_mix_u8_erase, vr_mixup_u8_erase: the uint8 entries above with the erase folded into the same
+ *   pass, bit-identical with vr_normalize_u8 -> vr_random_erase (-> vr_token_mix / vr_mixup): own pixels are erased under the own
+ *   sample's rectangles, a pixel taken from the partner carries the PARTNER's erase (its rectangles, its b), blends mix the two
+ *   erased values as before, vr_mixup's lam == 1 copy still carries the sample's own erase; targets are unaffected.  Every byte is
+ *   still read once and the partner only where it is used; only lanes whose pixels meet a rectangle of a sample they read run
+ *   Philox.  `erase` is a HOST struct, copied into the kernel arguments.
+ * As the entries they extend, and: VR_EINVAL a null erase / rects, R outside 1..4, an unknown mode; VR_EUNSUPPORTED B > 2^24,
+ * C > 4, W % 4; VR_EALIGN x not 16-byte or rects not 4-byte aligned.  Checked before anything is launched.
+ */
+enum { VR_ERASE_CONST = 0, VR_ERASE_RAND = 1, VR_ERASE_PIXEL = 2 };
+
+typedef struct vr_erase_rect {
+    int32_t y0, y1, x0, x1;
+} vr_erase_rect;    /* 16 bytes */
+
+typedef struct vr_erase_args {
+    const vr_erase_rect* rects;
+    int32_t R, mode;
+    uint64_t seed, call;
+} vr_erase_args;    /* 32 bytes */
+
+int vr_random_erase(float* x, int32_t B, int32_t C, int32_t H, int32_t W, const vr_erase_rect* rects, int32_t R, int32_t mode,
+                    uint64_t seed, uint64_t call, vr_stream_t stream);
+int vr_normalize_u8_erase(const uint8_t* in, float* out, int32_t B, int32_t C, int32_t H, int32_t W, const float* mean,
+                          const float* std, const vr_erase_args* erase, vr_stream_t stream);
+int vr_token_mix_u8_erase(const uint8_t* samples, float* out, const int64_t* labels, const int64_t* partner, float* targets,
+                          float* patch_targets, int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_classes, int32_t patch_len,
+                          int32_t half, int32_t y0, int32_t y1, int32_t x0, int32_t x1, float lam_patch, float oml_patch,
+                          float lam_img, float oml_img, float on_value, float off_value, const float* mean, const float* std,
+                          const vr_erase_args* erase, vr_stream_t stream);
+int vr_mixup_u8_erase(const uint8_t* samples, float* out, const int64_t* labels, float* targets, const vr_mixup_param* params,
+                      int32_t B, int32_t C, int32_t H, int32_t W, int32_t num_classes, float on_value, float off_value,
+                      const float* mean, const float* std, const vr_erase_args* erase, vr_stream_t stream);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

@@ -23,7 +23,19 @@ K = 1000, batch mode, once for a blend (lam = 0.37) and once for a cutmix (a 112
   t   pinned fp32 host batch -> device; timm's torch statements on the device batch (x.flip(0), mul_, add_ / the box assignment,
       mixup_target on the smoothed one-hots); two copy_ into the static x / t
 
-No model here: the lines alternate back to back.  f and u are checked to leave the same bits; whether t does is reported."""
+No model here: the lines alternate back to back.  f and u are checked to leave the same bits; whether t does is reported.
+
+--case erase: what random erasing costs inside the uint8 token mix (vitres.random_erasing.RandomErasing, the recipe's mode 'pixel',
+count 1; probability 0.25 -- the recipe's -- and 1.0), with the first protocol: B = 128, the uint8 batch resident on the device, into
+the static x / t / pt of the captured sr_tiny step, a replay between stages:
+
+  u   vr_token_mix_u8 as it is (no erase)
+  e   vr_token_mix_u8_erase
+  3   vr_normalize_u8 -> vr_random_erase -> vr_token_mix, the three stages e is specified by
+
+The 2 KB rectangle table of a batch is uploaded (pinned, non-blocking) in front of the timed stage: in training that copy is queued
+behind the previous step, here -- every stage starts on an idle device -- it would be timed as device time.  e and 3 are checked to
+leave the same bits.  Medians, quartiles and extremes per line."""
 import argparse
 import os
 import statistics
@@ -45,12 +57,14 @@ def main():
     ap.add_argument("--iters", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--out", default="")
-    ap.add_argument("--case", default="token_mix", choices=["token_mix", "mixup"])
+    ap.add_argument("--case", default="token_mix", choices=["token_mix", "mixup", "erase"])
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("input_bench.py times the GPU path and needs the MI355X")
     if args.case == "mixup":
         return mixup_case(args)
+    if args.case == "erase":
+        return erase_case(args)
     from vitres import engine, kernels as K
     from vitres.losses import SoftTargetCrossEntropy
     from vitres.optim import FlatAdamW
@@ -267,6 +281,125 @@ def mixup_case(args):
                 dev_bytes = (1 + partner[dn]) * N + 4 * N + T
                 row += " %6.1f MB %7.1f GB/s" % (dev_bytes / 1e6, dev_bytes / work / 1e6)
             out.append(row)
+    text = "\n".join(out)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+def erase_case(args):
+    import random
+
+    from vitres import engine, kernels as K
+    from vitres.losses import SoftTargetCrossEntropy
+    from vitres.optim import FlatAdamW
+    from vitres.random_erasing import RandomErasing
+    from vitres.token_mixup import SwitchTokenMix
+    dev = torch.device("cuda:0")
+    B, S = bench.WORKLOADS["sr_tiny_supernet"]["batch"], 224
+    mean, std = K.IMAGENET_DEFAULT_MEAN, K.IMAGENET_DEFAULT_STD
+    g = torch.Generator().manual_seed(0)
+    u8_dev = torch.randint(0, 256, (B, 3, S, S), dtype=torch.uint8, generator=g).to(dev)
+    labels = torch.randint(0, NC, (B,), generator=g).to(dev)
+    h = B // 2
+    draw = dict(half=h, partner=torch.cat([torch.randperm(h, generator=g), torch.randperm(B - h, generator=g) + h]),
+                box=(1, 3, 1, 3), lam_patch=1 - 4 / 16, lam_img=0.37)
+    mix_f, mix_u = SwitchTokenMix(PL, num_classes=NC), SwitchTokenMix(PL, num_classes=NC, input_norm=(mean, std))
+    probs = (0.25, 1.0)
+    tables = {p: RandomErasing(probability=p, rng=random.Random(0)).draw(B, S, S) for p in probs}     # the recipe's: pixel, count 1
+    share = {p: float(((t[:, 0, 1] - t[:, 0, 0]) * (t[:, 0, 3] - t[:, 0, 2])).sum()) / (B * S * S) for p, t in tables.items()}
+    seed = 0x5EED
+
+    torch.manual_seed(0)
+    model, _ = bench.build_model("sr_tiny_supernet", torch.bfloat16, dev)
+    model.train()
+    model.set_epoch(31)
+    opt = FlatAdamW(model, engine.param_groups_weight_decay(model, 0.05), lr=5e-4 * B / 512.0)
+    opt.own_shadow()
+    norm_out = torch.empty((B, 3, S, S), device=dev)
+    x0, t0, pt0, _ = mix_f(K.normalize_u8(u8_dev, mean, std, out=norm_out), labels, draw=draw)
+    step = engine.GraphedTrainStep(model, SoftTargetCrossEntropy(), x0, t0, pt0, "seq", optimizer=opt)
+    into = dict(out=step.x, targets_out=step.t, patch_targets_out=step.pt)
+    it = [0]
+
+    def replay():
+        opt.prepare_step()
+        step(step.x, step.t, step.pt, epoch=31, train_iter=it[0], arch_sample="multi")
+        it[0] += 1
+
+    def stage_u(p, ea):                                           # vr_token_mix_u8 as it is
+        mix_u(u8_dev, labels, draw=draw, **into)
+
+    def stage_e(p, ea):                                           # vr_token_mix_u8_erase
+        mix_u(u8_dev, labels, draw=dict(draw, erase=ea), **into)
+
+    def stage_3(p, ea):                                           # the three stages the fused entry is specified by
+        K.normalize_u8(u8_dev, mean, std, out=norm_out)
+        K.random_erase(norm_out, ea)
+        mix_f(norm_out, labels, draw=draw, **into)
+
+    stages = (("u vr_token_mix_u8 (no erase)", stage_u), ("e vr_token_mix_u8_erase", stage_e),
+              ("3 vr_normalize_u8 + vr_random_erase + vr_token_mix", stage_3))
+    for p in probs:                                               # the bits, before any timing
+        stage_e(p, K.erase_args(tables[p], "pixel", seed, 3, dev))
+        want = [b.clone() for b in (step.x, step.t, step.pt)]
+        for b in (step.x, step.t, step.pt):
+            b.zero_()
+        stage_3(p, K.erase_args(tables[p], "pixel", seed, 3, dev))
+        if not all(torch.equal(a.view(torch.int32), b.view(torch.int32)) for a, b in zip(want, (step.x, step.t, step.pt))):
+            sys.exit("input_bench.py: vr_token_mix_u8_erase does not reproduce the three stages' bits (probability %s)" % p)
+    times = {(name, p): [] for name, _ in stages for p in probs}
+    for i in range(args.warmup + args.iters):
+        for p in probs:
+            for name, fn in stages:
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ea = K.erase_args(tables[p], "pixel", seed, i, dev)        # (the 2 KB table goes up in front of the timed stage)
+                ev[0].record()
+                fn(p, ea)
+                ev[1].record()
+                replay()
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    times[(name, p)].append(ev[0].elapsed_time(ev[1]))
+    out = ["random erasing in the uint8 token mix, per batch: B = %d, 3 x %d x %d, patch_len %d, K = %d, mode 'pixel', count 1, uint8 batch "
+           "resident on the device, into the static x / t / pt of the captured sr_tiny step (bf16, replayed between stages); median of "
+           "%d after %d warm-up, HIP events, the lines alternating in one process; x / t / pt of e and 3 bit-identical"
+           % (B, S, S, PL, NC, args.iters, args.warmup)]
+    for p in probs:
+        out.append("probability %.2f (%.1f%% of the batch's pixels inside a rectangle):" % (p, 100 * share[p]))
+        med = {}
+        for name, _ in stages:
+            ts = times[(name, p)]
+            med[name[0]] = statistics.median(ts)
+            q = statistics.quantiles(ts, n=4)
+            out.append("  %-52s %7.3f ms (min %.3f, quartiles %.3f .. %.3f, max %.3f)" % (name, med[name[0]], min(ts), q[0], q[2], max(ts)))
+        out.append("  e - u = %+.3f ms (e / u = %.2f);  3 - e = %+.3f ms (3 / e = %.2f)" % (
+            med["e"] - med["u"], med["e"] / med["u"], med["3"] - med["e"], med["3"] / med["e"]))
+    # The lines above start every stage on an idle device, so whatever the host does before a stage's first launch is inside its time
+    # (e checks and marshals the table before its only launch; 3 does the same behind its first kernel).  A training loop keeps the
+    # device busy, so the second figure is the device's: 40 calls of a line queued back to back between two events, no replay.
+    out.append("the same lines queued back to back (40 calls between two events, no replay: the caches stay warm, the host's work is "
+               "hidden behind the device's); median of 7 such runs, ms per call:")
+    for p in probs:
+        ea = K.erase_args(tables[p], "pixel", seed, 0, dev)
+        per = {}
+        for name, fn in stages:
+            runs = []
+            for _ in range(7):
+                fn(p, ea)
+                torch.cuda.synchronize()
+                ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                ev[0].record()
+                for _ in range(40):
+                    fn(p, ea)
+                ev[1].record()
+                torch.cuda.synchronize()
+                runs.append(ev[0].elapsed_time(ev[1]) / 40)
+            per[name[0]] = (statistics.median(runs), min(runs), max(runs))
+        out.append("  probability %.2f: " % p + ";  ".join("%s %.4f (min %.4f max %.4f)" % ((k,) + per[k]) for k in "ue3")
+                   + ";  e - u = %+.4f, 3 - e = %+.4f" % (per["e"][0] - per["u"][0], per["3"][0] - per["e"][0]))
     text = "\n".join(out)
     print(text)
     if args.out:

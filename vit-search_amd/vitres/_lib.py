@@ -6,7 +6,7 @@ RuntimeError when the shared object is missing or does not export a declared sym
 """
 import ctypes
 import os
-from ctypes import c_float, c_int32, c_int64, c_void_p
+from ctypes import c_float, c_int32, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VITRES_LIB: another build of the same ABI (A/B timing of kernel changes on one box: tools/ab.sh)
@@ -57,6 +57,13 @@ class MixupParam(ctypes.Structure):
                 ("cutmix", c_int32), ("pad", c_int32)]
 
 
+class EraseArgs(ctypes.Structure):
+    _fields_ = [("rects", c_void_p), ("R", c_int32), ("mode", c_int32), ("seed", c_uint64), ("call", c_uint64)]
+
+
+VR_ERASE_CONST, VR_ERASE_RAND, VR_ERASE_PIXEL = 0, 1, 2
+
+
 # name -> argtypes ; every entry point returns int.  Must list every symbol of include/vitres_hip.h
 SYMBOLS = {
     "vr_version": [],
@@ -99,6 +106,11 @@ SYMBOLS = {
     "vr_token_mix_u8": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p, c_void_p, c_void_p],
     "vr_mixup": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p],
     "vr_mixup_u8": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p, c_void_p, c_void_p],
+    "vr_random_erase": [c_void_p] + [c_int32] * 4 + [c_void_p, c_int32, c_int32, c_uint64, c_uint64, c_void_p],
+    "vr_normalize_u8_erase": [c_void_p, c_void_p] + [c_int32] * 4 + [c_void_p, c_void_p, ctypes.POINTER(EraseArgs), c_void_p],
+    "vr_token_mix_u8_erase": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p, c_void_p, ctypes.POINTER(EraseArgs),
+                                                                               c_void_p],
+    "vr_mixup_u8_erase": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p, c_void_p, ctypes.POINTER(EraseArgs), c_void_p],
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],

@@ -8,7 +8,9 @@ training, the `vr_token_mix_u8` pass of `SwitchTokenMix(input_norm=...)` -- make
   ResidentU8Batches      a hold-out set kept on the device as uint8 (a quarter of its fp32 size), re-iterable: what
                          evo_eval.score_candidate / score_population and engine.evaluate take as `batches`.
 
-What is not here: decoding, augmentation and random erasing stay with the loader that produces the uint8 batches.
+What is not here: decoding and the geometric / colour augmentations stay with the loader that produces the uint8 batches.  Random
+erasing, which timm applies to the normalised image, cannot happen there any more: `erase=` (a vitres.random_erasing.RandomErasing)
+folds it into the normalising pass -- here with normalize=True, in the mix (`SwitchTokenMix(..., erase=)`, `Mixup(..., erase=)`) in training.
 """
 import torch
 
@@ -20,10 +22,15 @@ class DevicePrefetchLoader:
     `device` on a side stream while the current one is consumed, and every batch is yielded as (normalize_u8(batch), target) on the
     current stream.  normalize=False yields the uint8 device batch itself -- the training loop's form, where
     SwitchTokenMix(input_norm=(mean, std)) normalises inside the mix.  mean / std: per-channel, 0..1 units.  Pinned host batches
-    (pin_memory=True) make the copies asynchronous.  __len__, .sampler and .dataset are the wrapped loader's."""
+    (pin_memory=True) make the copies asynchronous.  erase=RandomErasing(...): every batch is yielded erased as well
+    (vr_normalize_u8_erase, the same pass); with normalize=False the mix owns the erase and erase= here raises.  __len__, .sampler
+    and .dataset are the wrapped loader's."""
 
-    def __init__(self, loader, device, mean=K.IMAGENET_DEFAULT_MEAN, std=K.IMAGENET_DEFAULT_STD, normalize=True):
-        self.loader, self.device, self.normalize = loader, torch.device(device), normalize
+    def __init__(self, loader, device, mean=K.IMAGENET_DEFAULT_MEAN, std=K.IMAGENET_DEFAULT_STD, normalize=True, erase=None):
+        if erase is not None and not normalize:
+            raise ValueError("DevicePrefetchLoader(normalize=False, erase=...): random erasing works on normalised pixels, so it "
+                             "belongs to whoever normalises -- pass erase= to SwitchTokenMix / Mixup(input_norm=...) instead")
+        self.loader, self.device, self.normalize, self.erase = loader, torch.device(device), normalize, erase
         self.norm = K.norm_constants(mean, std)
 
     def __len__(self):
@@ -62,6 +69,9 @@ class DevicePrefetchLoader:
             cur.wait_event(copied)
             u8.record_stream(cur)             # (allocated on the side stream, used on this one)
             target.record_stream(cur)
+        if self.erase is not None:
+            B, _, H, W = u8.shape
+            return K.normalize_u8_erase(u8, *self.norm, self.erase.next_args(B, H, W, u8.device if u8.is_cuda else None)), target
         return (K.normalize_u8(u8, *self.norm) if self.normalize else u8), target
 
 

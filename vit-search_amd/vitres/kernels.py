@@ -933,12 +933,26 @@ def mixup(x, labels, params, num_classes, on, off, norm=None, out=None, targets_
     them, a pixel box, the cutmix flag) and the mixed smoothed one-hot targets of the int64 `labels`; on / off: the one-hot values.
     The table is built in pinned host memory and uploaded on the current stream without a host wait.  Returns (out, targets):
     fresh fp32 tensors, or the contiguous fp32 out= [B,C,H,W] / targets_out= [B,num_classes] written in place; x is not modified."""
-    what = "vr_mixup" if norm is None else "vr_mixup_u8"
+    return _mixup(x, labels, params, num_classes, on, off, norm, None, out, targets_out)
+
+
+def mixup_u8_erase(x, labels, params, num_classes, on, off, norm, erase, out=None, targets_out=None):
+    """vr_mixup_u8_erase: mixup() on uint8 x with every sample erased (normalised space, its own rectangles and noise) before it is
+    mixed; erase: what erase_args() / RandomErasing.next_args() made.  The same bits as normalize_u8 -> random_erase -> mixup."""
+    if norm is None:
+        raise TypeError("vr_mixup_u8_erase normalises uint8 samples: norm = the pair norm_constants() made is required")
+    return _mixup(x, labels, params, num_classes, on, off, norm, erase, out, targets_out)
+
+
+def _mixup(x, labels, params, num_classes, on, off, norm, erase, out, targets_out):
+    what = "vr_mixup" if norm is None else "vr_mixup_u8" if erase is None else "vr_mixup_u8_erase"
     want = torch.float32 if norm is None else torch.uint8
     if x.dim() != 4 or x.dtype != want:
         raise TypeError("%s: a %s [B,C,H,W] tensor expected, got %s %s" % (what, want, x.dtype, tuple(x.shape)))
     B, C, H, W = x.shape
     params = check_mixup_params(params, B, H, W, what)
+    if erase is not None:
+        check_erase_rects(erase["rects"], B, H, W, what)
     if norm is not None and len(norm[0]) != C:
         raise ValueError("%s: %d channels but %d normalisation constants" % (what, C, len(norm[0])))
     _p(x)                                                          # (a CPU tensor is refused before anything is allocated)
@@ -955,6 +969,128 @@ def mixup(x, labels, params, num_classes, on, off, norm=None, out=None, targets_
     args = (_p(x), _p(out), _p(labels), _p(targets), _p(table), B, C, H, W, num_classes, float(np.float32(on)), float(np.float32(off)))
     if norm is None:
         _lib.check(_lib.lib().vr_mixup(*args, _stream()), what)
-    else:
+    elif erase is None:
         _lib.check(_lib.lib().vr_mixup_u8(*args, norm[0], norm[1], _stream()), what)
+    else:
+        ea, _table = _erase_struct(erase, dev, what)
+        _lib.check(_lib.lib().vr_mixup_u8_erase(*args, norm[0], norm[1], ctypes.byref(ea), _stream()), what)
     return out, targets
+
+
+# ---- timm's RandomErasing on the device (vr_random_erase and the *_erase forms of the uint8 entries; vitres/random_erasing.py draws)
+ERASE_MODES = {"const": _lib.VR_ERASE_CONST, "rand": _lib.VR_ERASE_RAND, "pixel": _lib.VR_ERASE_PIXEL}
+ERASE_MAX_RECTS = 4
+
+
+def check_erase_rects(rects, B, H, W, what="vr_random_erase"):
+    """rects as a contiguous int32 [B, R, 4] array of (y0, y1, x0, x1), 1 <= R <= 4, every rectangle inside H x W (empty ones are
+    legal).  As for the Mixup boxes the device cannot report a bad row, so the host copy is what is checked: RuntimeError VR_EINVAL,
+    before anything is launched."""
+    rects = np.ascontiguousarray(rects, dtype=np.int32)
+    if rects.ndim != 3 or rects.shape[0] != B or not 1 <= rects.shape[1] <= ERASE_MAX_RECTS or rects.shape[2] != 4:
+        raise ValueError("%s: the rectangle table has shape %s, expected (%d, 1..%d, 4)" % (what, rects.shape, B, ERASE_MAX_RECTS))
+    y0, y1, x0, x1 = (rects[..., i] for i in range(4))
+    bad = (y0 < 0) | (y0 > y1) | (y1 > H) | (x0 < 0) | (x0 > x1) | (x1 > W)
+    if bad.any():
+        b, r = (int(v[0]) for v in np.nonzero(bad))
+        raise RuntimeError("%s failed: %s: the rectangle [%d,%d) x [%d,%d) (number %d of sample %d) is not inside the %d x %d image"
+                           % (what, _lib._ERR[-1], y0[b, r], y1[b, r], x0[b, r], x1[b, r], r, b, H, W))
+    return rects
+
+
+def erase_args(rects, mode, seed, call, device=None):
+    """What the erase wrappers take: the host table int32 [B, R, 4] (kept for the check), the mode ('const', 'rand', 'pixel'), the
+    64-bit seed and call of the noise contract, and -- with `device` -- the table already on the device, copied from pinned memory on
+    the current stream without a host wait (otherwise the wrapper uploads it)."""
+    if mode not in ERASE_MODES:
+        raise ValueError("erase mode must be one of %s, got %r" % (sorted(ERASE_MODES), mode))
+    rects = np.ascontiguousarray(rects, dtype=np.int32)
+    args = dict(rects=rects, mode=mode, seed=int(seed) & (2 ** 64 - 1), call=int(call) & (2 ** 64 - 1), table=None)
+    if device is not None:
+        args["table"] = _upload_i32(rects, device)
+    return args
+
+
+def _upload_i32(array, dev):
+    host = torch.empty(array.shape, dtype=torch.int32, pin_memory=torch.device(dev).type == "cuda")
+    host.numpy()[...] = array
+    return host.to(dev, non_blocking=True)
+
+
+def _erase_struct(erase, dev, what):
+    """(the vr_erase_args struct, the device table it points to -- to be kept alive until the launch is issued)"""
+    rects = erase["rects"]                                                # (checked by the caller, before it allocated anything)
+    table = erase.get("table")
+    if table is None or table.device != dev:
+        table = _upload_i32(rects, dev)
+    if table.dtype != torch.int32 or tuple(table.shape) != rects.shape or not table.is_contiguous():
+        raise ValueError("%s: the device rectangle table must be a contiguous int32 tensor of shape %s" % (what, rects.shape))
+    return _lib.EraseArgs(_p(table), rects.shape[1], ERASE_MODES[erase["mode"]], erase["seed"], erase["call"]), table
+
+
+def random_erase(x, erase):
+    """vr_random_erase: timm's RandomErasing on a normalised fp32 [B,C,H,W] batch, IN PLACE, by the rectangles, mode, seed and
+    call of `erase` (erase_args() / RandomErasing.next_args()).  Returns x."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError("random_erase: a contiguous fp32 [B,C,H,W] tensor expected, got %s %s" % (x.dtype, tuple(x.shape)))
+    B, C, H, W = x.shape
+    check_erase_rects(erase["rects"], B, H, W)
+    _p(x)
+    ea, _table = _erase_struct(erase, x.device, "vr_random_erase")
+    _lib.check(_lib.lib().vr_random_erase(_p(x), B, C, H, W, ea.rects, ea.R, ea.mode, ea.seed, ea.call, _stream()), "vr_random_erase")
+    return x
+
+
+def normalize_u8_erase(u8, mean, std, erase, out=None):
+    """vr_normalize_u8_erase: normalize_u8 with the erase folded into the pass -- the bits of normalize_u8 then random_erase."""
+    if u8.dtype != torch.uint8 or u8.dim() != 4:
+        raise TypeError("normalize_u8_erase: a uint8 [B,C,H,W] tensor expected, got %s %s" % (u8.dtype, tuple(u8.shape)))
+    if not isinstance(mean, ctypes.Array):
+        mean, std = norm_constants(mean, std)
+    B, C, H, W = u8.shape
+    if len(mean) != C:
+        raise ValueError("normalize_u8_erase: %d channels but %d normalisation constants" % (C, len(mean)))
+    check_erase_rects(erase["rects"], B, H, W, "vr_normalize_u8_erase")
+    _p(u8)
+    u8 = u8.contiguous()
+    if out is None:
+        out = torch.empty((B, C, H, W), dtype=torch.float32, device=u8.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous():
+        raise ValueError("normalize_u8_erase: out must be a contiguous fp32 tensor of shape %s" % ((B, C, H, W),))
+    ea, _table = _erase_struct(erase, u8.device, "vr_normalize_u8_erase")
+    _lib.check(_lib.lib().vr_normalize_u8_erase(_p(u8), _p(out), B, C, H, W, mean, std, ctypes.byref(ea), _stream()),
+               "vr_normalize_u8_erase")
+    return out
+
+
+def token_mix_u8_erase(x, labels, draw, patch_len, num_classes, on, off, norm, erase, out=None, targets_out=None,
+                       patch_targets_out=None):
+    """vr_token_mix_u8_erase: SwitchTokenMix of the uint8 batch x by `draw` (vitres.token_mixup.SwitchTokenMix.draw: half, partner,
+    the box on the patch_len grid, lam_patch, lam_img) with every sample erased, in normalised space, before it is mixed -- the bits of
+    normalize_u8 -> random_erase -> vr_token_mix.  on / off: the smoothed one-hot values; norm: the pair norm_constants() made; erase:
+    erase_args() / RandomErasing.next_args().  Returns (out, targets, patch_targets): fresh fp32 tensors or the given ones."""
+    what = "vr_token_mix_u8_erase"
+    if x.dim() != 4 or x.dtype != torch.uint8:
+        raise TypeError("%s: a uint8 [B,C,H,W] tensor expected, got %s %s" % (what, x.dtype, tuple(x.shape)))
+    B, C, H, W = x.shape
+    check_erase_rects(erase["rects"], B, H, W, what)
+    _p(x)
+    x, dev, pl = x.contiguous(), x.device, patch_len
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if out is None else out
+    targets = torch.empty((B, num_classes), dtype=torch.float32, device=dev) if targets_out is None else targets_out
+    patch_targets = torch.empty((B, pl * pl, num_classes), dtype=torch.float32, device=dev) if patch_targets_out is None \
+        else patch_targets_out
+    for name, t, shape in (("out", out, (B, C, H, W)), ("targets_out", targets, (B, num_classes)),
+                           ("patch_targets_out", patch_targets, (B, pl * pl, num_classes))):
+        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError("%s must be a contiguous fp32 tensor of shape %s on %s" % (name, shape, dev))
+    partner = draw["partner"].to(dev, non_blocking=True)
+    labels = labels.to(dev).long().contiguous()
+    y0, y1, x0, x1 = draw["box"]
+    f32 = lambda v: float(np.float32(v))                                  # noqa: E731  torch rounds python scalars to fp32
+    ea, _table = _erase_struct(erase, dev, what)
+    _lib.check(_lib.lib().vr_token_mix_u8_erase(
+        _p(x), _p(out), _p(labels), _p(partner), _p(targets), _p(patch_targets), B, C, H, W, num_classes, pl, draw["half"], y0, y1, x0,
+        x1, f32(draw["lam_patch"]), f32(1. - draw["lam_patch"]), f32(draw["lam_img"]), f32(1. - draw["lam_img"]), f32(on), f32(off),
+        norm[0], norm[1], ctypes.byref(ea), _stream()), what)
+    return out, targets, patch_targets

@@ -12,6 +12,10 @@ the static input buffers of a captured hipGraph).
 `input_norm=(mean, std)` (0..1 units) makes the mix the normaliser of a uint8 input pipeline, as for vitres.token_mixup.SwitchTokenMix:
 the batch arrives as uint8 NCHW and one `vr_mixup_u8` pass reads the bytes, normalises as timm's PrefetchLoader does and mixes --
 the same bits as normalising first.
+
+`erase=RandomErasing(...)` (vitres/random_erasing.py) erases every sample before it is mixed, as the reference's loader transform does:
+uint8 batches take `vr_mixup_u8_erase` (still one pass); fp32 batches are copied, erased by `vr_random_erase` and mixed as before.
+The table of a call is left in `last_erase`; `draw=` replays it when the draw carries it as draw["erase"].
 """
 import numpy as np
 import torch
@@ -51,9 +55,20 @@ def param_table(draw, batch):
     return rows
 
 
+def erase_of(erase, draw, x):
+    """The erase arguments of one call of a mix on the batch x: the replayed ones (draw["erase"], what an earlier call left in
+    `last_erase`), else the next table of the mix's RandomErasing, else None."""
+    if draw.get("erase") is not None:
+        return draw["erase"]
+    if erase is None:
+        return None
+    B, _, H, W = x.shape
+    return erase.next_args(B, H, W, x.device if x.is_cuda else None)
+
+
 class Mixup:
     def __init__(self, mixup_alpha=1., cutmix_alpha=0., cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode='batch',
-                 correct_lam=True, label_smoothing=0.1, num_classes=1000, input_norm=None):
+                 correct_lam=True, label_smoothing=0.1, num_classes=1000, input_norm=None, erase=None):
         self.mixup_alpha, self.cutmix_alpha, self.cutmix_minmax = mixup_alpha, cutmix_alpha, cutmix_minmax
         if self.cutmix_minmax is not None:
             assert len(self.cutmix_minmax) == 2
@@ -65,6 +80,7 @@ class Mixup:
         self.mixup_enabled = True                                 # (timm: set to False to turn mixing off)
         # (mean, std) in uint8 units as two host float arrays, or None: the samples arrive normalised
         self.input_norm = None if input_norm is None else K.norm_constants(*input_norm)
+        self.erase, self.last_erase = erase, None                 # a vitres.random_erasing.RandomErasing, or None
 
     @property
     def normalizes(self):
@@ -169,5 +185,12 @@ class Mixup:
         off = self.label_smoothing / self.num_classes
         on = 1. - self.label_smoothing + off
         x = x if self.input_norm is not None else x.float()
-        return K.mixup(x, target, param_table(d, B), self.num_classes, on, off, norm=self.input_norm, out=out,
+        ea = self.last_erase = erase_of(self.erase, d, x)
+        if ea is None:
+            return K.mixup(x, target, param_table(d, B), self.num_classes, on, off, norm=self.input_norm, out=out,
+                           targets_out=targets_out)
+        if self.input_norm is not None:
+            return K.mixup_u8_erase(x, target, param_table(d, B), self.num_classes, on, off, self.input_norm, ea, out=out,
+                                    targets_out=targets_out)
+        return K.mixup(K.random_erase(x.clone().contiguous(), ea), target, param_table(d, B), self.num_classes, on, off, out=out,
                        targets_out=targets_out)

@@ -11,19 +11,25 @@ mixes; the tensor work is one `vr_token_mix` call (two streaming kernels).  Retu
 `input_norm=(mean, std)` (0..1 units, e.g. the ImageNet defaults) makes the mix the normaliser of a uint8 input pipeline: the
 batch arrives as uint8 NCHW (timm's fast_collate; `vitres.data.DevicePrefetchLoader(..., normalize=False)`) and one
 `vr_token_mix_u8` pass reads the bytes, normalises as timm's PrefetchLoader does and mixes -- the same bits as normalising first.
+
+`erase=RandomErasing(...)` (vitres/random_erasing.py) erases every sample before it is mixed, as the reference's loader transform does:
+uint8 batches take `vr_token_mix_u8_erase` (still one pass); fp32 batches are copied, erased by `vr_random_erase` and mixed as before.
+The table of a call is left in `last_erase`; `draw=` replays it when the draw carries it as draw["erase"].
 """
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, kernels
 from .kernels import _p, _stream, norm_constants
+from .mixup import erase_of
 
 
 class SwitchTokenMix:
-    def __init__(self, patch_len, switch_prob=0.5, num_classes=1000, smoothing=0.1, input_norm=None):
+    def __init__(self, patch_len, switch_prob=0.5, num_classes=1000, smoothing=0.1, input_norm=None, erase=None):
         self.patch_len, self.switch_prob, self.num_classes, self.smoothing = patch_len, switch_prob, num_classes, smoothing
         # (mean, std) in uint8 units as two host float arrays, or None: the samples arrive normalised
         self.input_norm = None if input_norm is None else norm_constants(*input_norm)
+        self.erase, self.last_erase = erase, None                 # a vitres.random_erasing.RandomErasing, or None
 
     @property
     def normalizes(self):
@@ -65,6 +71,25 @@ class SwitchTokenMix:
 
     def __call__(self, samples, targets, out=None, draw=None, targets_out=None, patch_targets_out=None):
         self.check_dtype(samples)
+        if self.erase is not None or (draw is not None and draw.get("erase") is not None):
+            return self._erase_and_mix(samples, targets, out, draw, targets_out, patch_targets_out)
+        return self._mix(samples, targets, out, draw, targets_out, patch_targets_out)
+
+    def _erase_and_mix(self, samples, targets, out, draw, targets_out, patch_targets_out):
+        B, C, H, W = samples.shape
+        d = draw or self.draw(B)
+        ea = self.last_erase = erase_of(self.erase, d, samples)
+        if self.input_norm is None:                               # fp32: erase a copy, then the mix as it is
+            x = kernels.random_erase(samples.float().clone(memory_format=torch.contiguous_format), ea)
+            return self._mix(x, targets, out, d, targets_out, patch_targets_out)
+        if len(self.input_norm[0]) != C:
+            raise ValueError('input_norm has %d channels, the samples %d' % (len(self.input_norm[0]), C))
+        off = self.smoothing / self.num_classes
+        res = kernels.token_mix_u8_erase(samples, targets, d, self.patch_len, self.num_classes, 1. - self.smoothing + off, off,
+                                         self.input_norm, ea, out=out, targets_out=targets_out, patch_targets_out=patch_targets_out)
+        return res + ('seq',)
+
+    def _mix(self, samples, targets, out, draw, targets_out, patch_targets_out):
         if not samples.is_cuda:
             raise RuntimeError('vitres.token_mixup runs on the GPU through libvitres_hip.so (CPU restatement: oracle/)')
         B, C, H, W = samples.shape
