@@ -156,6 +156,23 @@ typedef struct vr_gemm_args {
                             turns the split on: every real split measured slower than the unsplit kernel on the step's shapes,
                             DESIGN.md), 2 - 4 = that many shares wherever the form has a split kernel and ws holds tiles x shares
                             slabs of the tile's fp32 size */
+    /* Glue of the spatial-reduction block and of the patch embedding folded into the GEMM that touches the same rows
+       (nets/vit_sr_supernet.py:114-172,398-407).  Forward bf16 / fp16 forms with an fp32 result only (gemm_nt.hip; N % 8 == 0,
+       ldc % 8 == 0, no act / dact_u / a_trans / b_trans / atomic), VR_EUNSUPPORTED anywhere else.  All zero / NULL: none of it. */
+    const float* sr_x;   /* pooled shortcut: fp32 [batch, sr_tokens + sr_g^2, sr_cin], the block's input stream.  Output row
+                            (sample s, m = oh * (sr_g/2) + ow) gets, where resid would be added and for columns n < sr_cin,
+                            0.25f * (((p00 + p01) + p10) + p11), p_ij = sr_x[s][sr_tokens + (2 oh + i) sr_g + 2 ow + j][n] -- what
+                            vr_sr_resid writes and a resid read of it adds.  rows_in == (sr_g/2)^2, sr_cin % 8 == 0; no resid / scale */
+    const int32_t* keep_out; /* [batch] or NULL: columns n >= keep_out[s] are stored as exact 0, after every other term (vr_mask_rows
+                            on the result).  Not together with keep_n */
+    const float* tok_src; /* tok_rows > 0: the launch also stores the tok_rows leading token rows of every sample's output block -- row
+                            s * c_map.rps + t, t < tok_rows == c_map.off, c_map.rpi == rows_in -- written by the workgroups that hold the
+                            sample's first GEMM row:  C[.][n] = (n < tok_cols ? tok_src[(s * tok_rps + t) * tok_ld + n] : 0)
+                            (+ tok_pos[t * N + n]), 0 for n >= keep_out[s] (or keep_n[s]).  tok_rps == 0: the same rows for every sample */
+    const float* tok_pos; /* fp32 [tok_rows, N] or NULL */
+    int32_t sr_g, sr_cin, sr_tokens;
+    int32_t tok_rows, tok_ld, tok_rps, tok_cols;
+    int32_t reserved0;
 } vr_gemm_args;
 
 /* bytes of vr_gemm_args.ws that enable tile sharing on the current device */
@@ -334,6 +351,21 @@ int vr_ln_bwd(const void* dy, const float* x, const float* w, const float* mean,
               const int32_t* keep, const float* dx_in, float* dx_out, float* dw, float* db,
               void* gt_out, const float* gt_scale, const int32_t* gt_keep,
               int32_t M, int32_t C, int32_t rows_per_sample, int32_t dy_dtype, int32_t grad_copies, vr_stream_t stream);
+
+/*
+ * vr_ln_bwd of the LayerNorm of a spatial-reduction block (nets/vit_sr_supernet.py:114-172), bf16, reading dy and dx_in where the
+ * block's backward already holds them instead of from tensors written by vr_sr_col2im / vr_sr_resid_bwd.  The M = B * (T + g*g)
+ * rows are those of the block's input (T = num_tokens leading token rows per sample, then the g x g patch rows):
+ *   patch row (ih, iw): dy = bf16(sum of the taps (kh, kw) of dcol [B * (g/2)^2, 9 C] that vr_sr_col2im sums, in its order, in fp32)
+ *   token row t:        dy = dy_tok[b * T + t]                     (bf16 [B * T, C], the token Linear's data gradient)
+ *   dx_in = f * gout[parent row][c]; gout fp32 [B, T + (g/2)^2, Cout], Cout >= C; the parent of a patch row is the pooled row
+ *           T + (ih/2) * (g/2) + iw/2 with f = 1/4, that of token row t is row t with f = 1  (what vr_sr_resid_bwd writes)
+ * Every output (dx_out, dw / db with grad_copies, gt_out) is bit for bit vr_ln_bwd's on those tensors.  C % 8 == 0, Cout % 4 == 0.
+ */
+int vr_ln_bwd_sr(const void* dcol, const void* dy_tok, const float* gout, const float* x, const float* w, const float* mean,
+                 const float* rstd, const int32_t* keep, float* dx_out, float* dw, float* db,
+                 void* gt_out, const float* gt_scale, const int32_t* gt_keep,
+                 int32_t B, int32_t g, int32_t C, int32_t Cout, int32_t num_tokens, int32_t grad_copies, vr_stream_t stream);
 
 /*
  * Fold the partial rows written by vr_ln_bwd / vr_gemm_ln (mode 1) with grad_copies = `copies` into the LayerNorm parameter

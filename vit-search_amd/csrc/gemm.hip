@@ -811,15 +811,41 @@ static int gemm_validate(vr_gemm_args& a) {
 // tickets (16 KB) + four 128 x 128 fp32 slabs per CU: the workspace of the K-split kernels (gemm_ntk.hip SPLIT, vr_gemm_args.k_shares)
 extern "C" int vr_gemm_ws_bytes(void) { return (int)(4096 * 4 + (size_t)cu_count() * 2 * (256 * 128) * sizeof(float)); }
 
+// sr_x / keep_out / tok_rows (include/vitres_hip.h): 0 = none asked for, 1 = asked for and well formed, < 0 = error
+static int fold_validate(const vr_gemm_args& a) {
+    if (!a.sr_x && !a.keep_out && a.tok_rows <= 0) return 0;
+    if (a.tok_rows < 0) return VR_EINVAL;
+    if (a.a_trans || a.b_trans || a.atomic || a.act || a.dact_u || a.C2 || a.out_dtype != VR_F32 || a.in_dtype == VR_F32 || a.N % 8 ||
+        a.ldc % 8 || a.n_period > 0 || a.rows_in <= 0 || (a.keep_out && a.keep_n))
+        return VR_EUNSUPPORTED;
+    if (a.sr_x) {
+        const int go = a.sr_g / 2;
+        if (a.sr_g <= 0 || (a.sr_g & 1) || a.sr_tokens < 0 || a.rows_in != go * go) return VR_EINVAL;
+        if (a.sr_cin <= 0 || a.sr_cin % 8 || a.sr_cin > a.N || a.resid || a.scale) return VR_EUNSUPPORTED;
+        if ((uintptr_t)a.sr_x & 15) return VR_EALIGN;
+        if ((long long)((a.M + a.rows_in - 1) / a.rows_in) * (a.sr_tokens + a.sr_g * a.sr_g) > 0x7fffffffLL) return VR_EUNSUPPORTED;
+    }
+    if (a.tok_rows > 0) {
+        if (!a.tok_src || a.c_map.rpi != a.rows_in || a.c_map.off != a.tok_rows || a.c_map.rps < a.rows_in + a.tok_rows || a.tok_rps < 0)
+            return VR_EINVAL;
+        if (a.tok_cols <= 0 || a.tok_cols % 4 || a.tok_ld % 4 || a.tok_ld < a.tok_cols || a.tok_cols > a.N) return VR_EUNSUPPORTED;
+        if (((uintptr_t)a.tok_src & 15) || ((uintptr_t)a.tok_pos & 15)) return VR_EALIGN;
+    }
+    return 1;
+}
+
 extern "C" int vr_gemm(const vr_gemm_args* args, vr_stream_t stream) {
     if (!args) return VR_EINVAL;
     vr_gemm_args a = *args;
     const int vrc = gemm_validate(a);
     if (vrc != VR_OK) return vrc;
+    const int frc = fold_validate(a);
+    if (frc < 0) return frc;
     if (!(a.sched & 4) && vr_gemm_nt_launch(a, (hipStream_t)stream, cu_count())) {
         VR_CHECK_LAUNCH();
         return VR_OK;
     }
+    if (frc > 0) return VR_EUNSUPPORTED;               // the folded glue exists in gemm_nt.hip's kernels only
     if (!(a.sched & 4) && vr_gemm_tn_launch(a, (hipStream_t)stream, cu_count())) {
         VR_CHECK_LAUNCH();
         return VR_OK;

@@ -52,7 +52,9 @@ __device__ const uint4 zero_chunk[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}
 
 // TI: 16-bit operand type (bf16_t; f16_t for the forward forms of the fp16 mode)
 template <typename TI, typename TO, int EPI, bool FAST, int MI, int NJ, int STAGES, int FEAT, bool BKM = false>
-__global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm_args p) {
+// (FEAT 6 holds four pooled rows per output row in its epilogue: at the 4 / 5 workgroup register caps it spills, and asked for them
+// on the 64 x 128 two-slice form -- three workgroups per CU by LDS -- the compiler settled for two)
+__global__ __launch_bounds__(NTHR, FEAT == 6 ? 3 : (MI == 4 ? 4 : 5)) void nt_kernel(const vr_gemm_args p) {
     constexpr int BM = 32 * MI, WROWS = 16 * MI;      // tile rows, rows per wave
     constexpr int BN = 32 * NJ, WCOLS = 16 * NJ;      // tile columns, columns per wave
     constexpr int A_BYTES = BM * BK * 2, AP = MI;     // A slice bytes, LDS-DMA pieces of A per wave
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm
         }
     }
     const char* zero = reinterpret_cast<const char*>(zero_chunk);
-    const bool ktail = (FEAT == 4 || BKM) && (p.K % BK) != 0;   // FEAT 0..3: K % 64 == 0 (host check; BKM: checked here)
+    const bool ktail = (FEAT >= 4 || BKM) && (p.K % BK) != 0;   // FEAT 0..3: K % 64 == 0 (host check; BKM: checked here)
 
     // ---- fragment read offsets: lane -> row (lane & 15) of a 16-row group, k-chunk 4 s + (lane >> 4) ----
     const int frow = lane & 15, fswz = (frow >> 1) & 7;
@@ -232,6 +234,13 @@ __global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm
                 rm.orow = (int)map_row({p.c_map.rpi, p.c_map.rps, p.c_map.off}, m);
                 if (p.scale) rm.scale = p.scale[sample];
                 if (p.keep_n) rm.keep = p.keep_n[sample];
+                if constexpr (FEAT >= 5) {
+                    if (p.keep_out) rm.keep = p.keep_out[sample];
+                }
+                if constexpr (FEAT == 6) {                          // the 2 x 2 patch rows pooled into this output row start here
+                    const int go = p.sr_g >> 1, oh = rm.mloc / go, ow = rm.mloc - oh * go;
+                    rm.srow = sample * (p.sr_tokens + p.sr_g * p.sr_g) + p.sr_tokens + 2 * oh * p.sr_g + 2 * ow;
+                }
             }
             rowmeta[t] = rm;
         }
@@ -315,6 +324,34 @@ __global__ __launch_bounds__(NTHR, MI == 4 ? 4 : 5) void nt_kernel(const vr_gemm
     // measured round 3: +10..17 registers, 4 - 12 spilled at the 128 / 96 caps, residual GEMMs 29.0 -> 30.1 / 19.3 -> 21.0 us: no)
     epilogue<TO, EPI, FAST, MI, NJ, FEAT>(p, acc, reinterpret_cast<float*>(smem + wave * 4096), rowmeta + wm * WROWS, n0 + wn * WCOLS,
                                          lane);
+    if constexpr (FEAT >= 5) {
+        // token rows of the output (vr_gemm_args.tok_src): the tile that holds a sample's first GEMM row also stores that sample's
+        // tok_rows leading rows for its own columns -- a few rows per tile, plain 16-byte stores, nobody waits for them
+        if (p.tok_rows > 0) {
+            const int P = p.rows_in, mend = min(m0 + BM, p.M);
+            const int s0 = (m0 + P - 1) / P, s1 = (mend - 1) / P + 1;          // samples s with m0 <= s P < mend
+            constexpr int C4 = BN / 4;
+            const int per = p.tok_rows * C4;
+            const int32_t* kp = p.keep_out ? p.keep_out : p.keep_n;
+            for (int idx = t; idx < (s1 - s0) * per; idx += NTHR) {
+                const int s = s0 + idx / per, rem = idx % per;
+                const int tr = rem / C4, c = n0 + (rem % C4) * 4;
+                if (c >= p.N) continue;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c < p.tok_cols) v = *reinterpret_cast<const float4*>(p.tok_src + ((long long)s * p.tok_rps + tr) * p.tok_ld + c);
+                if (p.tok_pos) {
+                    const float4 q4 = *reinterpret_cast<const float4*>(p.tok_pos + (long long)tr * p.N + c);
+                    v.x += q4.x; v.y += q4.y; v.z += q4.z; v.w += q4.w;
+                }
+                const int kc = kp ? kp[s] : p.N;
+                if (c + 0 >= kc) v.x = 0.f;
+                if (c + 1 >= kc) v.y = 0.f;
+                if (c + 2 >= kc) v.z = 0.f;
+                if (c + 3 >= kc) v.w = 0.f;
+                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + ((long long)s * p.c_map.rps + tr) * p.ldc + c) = v;
+            }
+        }
+    }
     NT_STAMP(5);
 }
 
@@ -334,7 +371,9 @@ template <typename TI, typename TO, int EPI, int MI, int NJ, int STAGES = 1> voi
     }
     // epilogue form (see nt_kernel): the forms of the transformer-block Linears get their own kernels
     int feat = 4;
-    if (fast && !a.pos && a.K % BK == 0) {
+    const bool fold = a.sr_x || a.keep_out || a.tok_rows > 0;      // (vr_gemm admitted the form: fast, fp32 result, plain store)
+    if (fold) feat = a.sr_x ? 6 : 5;
+    else if (fast && !a.pos && a.K % BK == 0) {
         if (!a.bias && !a.resid && !a.scale) feat = 0;
         else if (a.bias && !a.resid && !a.scale) feat = 1;
         else if (a.bias && a.resid && !a.scale) feat = 2;
@@ -346,6 +385,12 @@ template <typename TI, typename TO, int EPI, int MI, int NJ, int STAGES = 1> voi
             case 1: return launch3<TI, TO, EPI, MI, NJ, STAGES, 1>(a, stream, fast);
             case 2: return launch3<TI, TO, EPI, MI, NJ, STAGES, 2>(a, stream, fast);
             case 3: return launch3<TI, TO, EPI, MI, NJ, STAGES, 3>(a, stream, fast);
+            case 5:
+                if constexpr (sizeof(TO) == 4) return launch3<TI, TO, EPI, MI, NJ, STAGES, 5>(a, stream, fast);
+                return;
+            case 6:
+                if constexpr (sizeof(TO) == 4) return launch3<TI, TO, EPI, MI, NJ, STAGES, 6>(a, stream, fast);
+                return;
             default: return launch3<TI, TO, EPI, MI, NJ, STAGES, 4>(a, stream, fast);
         }
     } else if constexpr (EPI == EPI_GELU) {
@@ -391,6 +436,7 @@ bool vr_gemm_nt_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu) {
     const bool f16 = a.in_dtype == VR_F16;
     if ((a.in_dtype != VR_BF16 && !f16) || a.a_trans || a.atomic || a.split_k > 1 || a.bias_grad) return false;
     if (f16 && (a.b_trans || a.dact_u)) return false;                  // fp16: the forward forms only
+    if ((a.sr_x || a.keep_out || a.tok_rows > 0) && (a.sched & 0x80000)) return false;
     if (vr_gemm_ntk_launch(a, stream, n_cu, nullptr)) return true;
     // sched bit 0x80000: the operand may hold unwritten (fully masked) tiles, readable only by the group-pure row tiling of
     // gemm_ntk.hip -- the kernels below tile across architecture groups: refused (vr_gemm then fails loudly)

@@ -19,7 +19,10 @@ constexpr int BK = 64;
 // per-row epilogue metadata, computed once per tile while the first slices are in flight
 struct RowMeta {
     int keep;      // kept output-column prefix of the row's sample (1 << 30: dense)
-    float scale;   // DropPath scale of the row's sample
+    union {
+        float scale;   // DropPath scale of the row's sample
+        int srow;      // FEAT 6 (pooled shortcut -- no scale there): row of sr_x that holds p00 of this output row
+    };
     int orow;      // output row after c_map, -1: row >= M
     int mloc;      // row index inside its sample (pos-embed row)
 };
@@ -54,7 +57,8 @@ template <int ROWB> __device__ __forceinline__ bfv8 tr_frag(const char* p) {
 // or entirely outside the matrix, so the epilogue is branch-free 16-byte accesses.
 // FEAT (FAST kernels): which optional epilogue terms exist is a compile-time fact of the kernel -- 0: none, 1: bias, 2: bias +
 // residual, 3: bias + residual + DropPath scale, 4: decided per launch from the arguments (pos-embed, any other mix; the only
-// form of the non-FAST kernels).  As run-time uniform conditions the compiler if-converts them into a v_cndmask per element
+// form of the non-FAST kernels), 5: 4 plus the outer mask keep_out (and, in nt_kernel, the token rows tok_src), 6: 5 plus the pooled
+// shortcut sr_x of the spatial-reduction block (both FAST only, fp32 result).  As run-time uniform conditions the compiler if-converts them into a v_cndmask per element
 // and term (measured: 890 VALU instructions per tile and wave against 128 MFMAs at K = 256, VALU pipe busy 2x the matrix pipe).
 // DEPTH: rounds of side operands in flight.  The fp32 residual costs 16 registers per round; with ONE round in flight (the load
 // at the top of its own round) every round exposes a whole HBM latency: stamps put the residual epilogue of a 128 x 128 tile at
@@ -84,7 +88,10 @@ __device__ __forceinline__ void epilogue(const vr_gemm_args& p, f32x4 (&acc)[MI]
     // group never wraps; other periods take the per-element test)
     const bool grp = FAST || p.n_period <= 0 || (p.n_period & 7) == 0;
     const int ncp = p.n_period > 0 ? nc % p.n_period : nc;
-    constexpr bool GEN = FEAT == 4;
+    constexpr bool GEN = FEAT >= 4;
+    constexpr bool SRF = FEAT == 6, KOUT = FEAT >= 5;
+    const bool has_kout = KOUT && p.keep_out != nullptr;      // (RowMeta.keep holds keep_out then: never together with keep_n)
+    const int scol = nc < p.sr_cin ? nc : 0;                   // sr_cin % 8 == 0: the lane's group is whole or beyond the input width
     const bool has_bias = (EPI == EPI_STORE || EPI == EPI_GELU) && (GEN ? p.bias != nullptr : FEAT >= 1);
     const bool has_pos = (EPI == EPI_STORE) && GEN && p.pos;
     const bool has_res = (EPI == EPI_STORE) && (GEN ? p.resid != nullptr : FEAT >= 2);
@@ -195,6 +202,16 @@ __device__ __forceinline__ void epilogue(const vr_gemm_args& p, f32x4 (&acc)[MI]
         for (int q = 0; q < NQ; ++q) {
             const int rl = q * RPP + (lane / LPR);
             const bool mok = rm[q].orow >= 0;
+            float4 sx[4][2];                                        // SRF: the four pooled rows of this row, 8 x 16 bytes in flight
+            if constexpr (SRF) {                                    // (one row group at a time: both groups' 64 registers cost a wave per SIMD)
+                const float* x0 = p.sr_x + (long long)(mok ? rm[q].srow : 0) * p.sr_cin + scol;      // clamped, never branched around
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const float* xr = x0 + ((r4 >> 1) * p.sr_g + (r4 & 1)) * (long long)p.sr_cin;
+                    sx[r4][0] = *reinterpret_cast<const float4*>(xr);
+                    sx[r4][1] = *reinterpret_cast<const float4*>(xr + 4);
+                }
+            }
             float v[CW];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -268,6 +285,30 @@ __device__ __forceinline__ void epilogue(const vr_gemm_args& p, f32x4 (&acc)[MI]
                     if (has_res) {
 #pragma unroll
                         for (int e = 0; e < CW; ++e) v[e] += rv[q][e];
+                    }
+                }
+                if constexpr (SRF) {
+                    {
+                        // vr_sr_resid's value in its operand order; kept out of an fma with the add (the separate path adds a stored value)
+                        const bool in = nc < p.sr_cin;
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            float4 s4;
+                            s4.x = 0.25f * (((sx[0][h].x + sx[1][h].x) + sx[2][h].x) + sx[3][h].x);
+                            s4.y = 0.25f * (((sx[0][h].y + sx[1][h].y) + sx[2][h].y) + sx[3][h].y);
+                            s4.z = 0.25f * (((sx[0][h].z + sx[1][h].z) + sx[2][h].z) + sx[3][h].z);
+                            s4.w = 0.25f * (((sx[0][h].w + sx[1][h].w) + sx[2][h].w) + sx[3][h].w);
+                            asm volatile("" : "+v"(s4.x), "+v"(s4.y), "+v"(s4.z), "+v"(s4.w));
+                            v[4 * h] += in ? s4.x : 0.f; v[4 * h + 1] += in ? s4.y : 0.f;
+                            v[4 * h + 2] += in ? s4.z : 0.f; v[4 * h + 3] += in ? s4.w : 0.f;
+                        }
+                    }
+                }
+                if constexpr (KOUT) {
+                    if (has_kout) {
+                        const int kn = rm[q].keep - nc;
+#pragma unroll
+                        for (int e = 0; e < CW; ++e) v[e] = e < kn ? v[e] : 0.f;
                     }
                 }
                 if (any) storew<TO, CW, WT && EPI == EPI_STORE>(p.C, oidx[q], v, vec, mok, nvalid);

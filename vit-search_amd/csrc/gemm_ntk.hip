@@ -574,6 +574,7 @@ bool vr_gemm_panel_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu); 
 // tickets in a.ws; anything else returns false and nothing is launched.
 bool vr_gemm_ntk_launch(const vr_gemm_args& a, hipStream_t stream, int n_cu, const vr_ln_epilogue* ln) {
     using namespace vr_gemm_nt;
+    if (a.sr_x || a.keep_out || a.tok_rows > 0) return false;       // the folded spatial-reduction / embedding glue: gemm_nt.hip only
     if (ln) {
         if (a.out_dtype != VR_F32 || !a.bias || !a.resid || a.b_trans || a.dact_u || a.act || a.c_map.rpi || a.ldc != a.N || a.N % 4 ||
             a.N > 2048 || !a.ws || a.ws_bytes < SPLIT_TICKET_BYTES || group_tiles(a.M, 64, a.m_groups) > 2048 || ln->mode != 0 || !ln->w ||

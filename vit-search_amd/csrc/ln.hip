@@ -117,14 +117,25 @@ template <> __device__ __forceinline__ float4 load4<bf16_t>(const bf16_t* p) {
 
 // rows per workgroup are chosen per launch: more rows = fewer dgamma/dbeta atomics, fewer rows = more workgroups
 
-template <typename TI, int MAXV>
+// SR form (vr_ln_bwd_sr): the LayerNorm of a spatial-reduction block.  Its dy and dx_in are not tensors of their own: a patch
+// row's dy is the col2im sum of at most four taps of the conv data gradient `dcol` (summed in fp32 in (kh, kw) order, rounded
+// to bf16: the bits sr_col2im_v8_kernel would have stored), a token row's dy is a row of the small token data gradient, and
+// dx_in is the 2x2-mean shortcut's gradient f * gout[parent row] (f = 1/4 for patch rows, 1 for token rows).
+struct SrSrc {
+    const bf16_t* dcol;   // [B * (g/2)^2, 9 C]
+    const bf16_t* dytok;  // [B * NT, C]
+    const float* gout;    // [B * (NT + (g/2)^2), Cout]
+    int g, NT, Cout;
+};
+
+template <typename TI, int MAXV, bool SR>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const TI* __restrict__ dy, const float* __restrict__ x,
                                                      const float* __restrict__ w, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const int* __restrict__ keep,
                                                      const float* __restrict__ dx_in, float* __restrict__ dx_out,
                                                      float* __restrict__ dw, float* __restrict__ db, TI* __restrict__ gt_out,
                                                      const float* __restrict__ gt_scale, const int* __restrict__ gt_keep,
-                                                     int M, int C, int rps, int BWD_ROWS, int copies, int xcd) {
+                                                     int M, int C, int rps, int BWD_ROWS, int copies, int xcd, SrSrc sr) {
     __shared__ float red[2][4][64 * 4];  // [dw|db][wave][lane*4+e], reused per j
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float4 gw[MAXV], gb[MAXV], ww[MAXV];
@@ -142,6 +153,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TI* __restrict__ dy, 
         int kc[RU], k2[RU];
         float mu[RU], rs[RU], sc2[RU];
         bool rok[RU];
+        uint2 raw[SR ? RU : 1][SR ? MAXV : 1][4];                    // SR: the row's taps, all in flight with x and gout
+        bool tv[SR ? RU : 1][4], tok[SR ? RU : 1];
+        float fr[SR ? RU : 1];
+        const bf16_t* tp[4];
+        const float* gsrc;
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
             const int m = mbeg + rr + 4 * u;
@@ -152,14 +168,61 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TI* __restrict__ dy, 
             sc2[u] = (gt_out && gt_scale) ? gt_scale[mc / rps] : 1.0f;
             mu[u] = mean[mc];
             rs[u] = rstd[mc];
+            if constexpr (SR) {
+                // the row's sources (wave-uniform): slot t of a patch row is tap (kh, kw) in sr_col2im_v8_kernel's order -- an odd
+                // ih takes kh = 0 (oh = (ih+1)/2, outside at the bottom edge) then kh = 2, an even ih only kh = 1; same for iw
+                const int ms = __builtin_amdgcn_readfirstlane(mc);
+                const int b = ms / rps, r = ms - b * rps, go = sr.g >> 1;
+                tok[u] = r < sr.NT;
+                fr[u] = tok[u] ? 1.0f : 0.25f;
+                const int q = tok[u] ? 0 : r - sr.NT;
+                const int ih = q / sr.g, iw = q - ih * sr.g;
+                const int kh[2] = {(ih & 1) ? 0 : 1, 2}, oh[2] = {(ih + 1) >> 1, (ih - 1) >> 1};
+                const int kw[2] = {(iw & 1) ? 0 : 1, 2}, ow[2] = {(iw + 1) >> 1, (iw - 1) >> 1};
+                const bool hv[2] = {oh[0] < go, (ih & 1) != 0}, wv[2] = {ow[0] < go, (iw & 1) != 0};
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    tv[u][t] = tok[u] ? t == 0 : (hv[t >> 1] && wv[t & 1]);
+                    const long long off = ((long long)(b * go + oh[t >> 1]) * go + ow[t & 1]) * 9 * C + (kh[t >> 1] * 3 + kw[t & 1]) * C;
+                    tp[t] = tok[u] ? sr.dytok + (long long)(b * sr.NT + r) * C : sr.dcol + (tv[u][t] ? off : 0);   // clamped
+                }
+                gsrc = sr.gout + ((long long)b * (sr.NT + go * go) + (tok[u] ? r : sr.NT + (ih >> 1) * go + (iw >> 1))) * sr.Cout;
+            }
 #pragma unroll
             for (int j = 0; j < MAXV; ++j) {
                 const int c = (lane + 64 * j) * 4;
                 const int cc = c < C ? c : 0;                        // clamped: loads are never branched around
-                gv[u][j] = load4<TI>(dy + (long long)mc * C + cc);
+                if constexpr (SR) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) raw[u][j][t] = *reinterpret_cast<const uint2*>(tp[t] + cc);
+                    rv[u][j] = *reinterpret_cast<const float4*>(gsrc + cc);
+                } else {
+                    gv[u][j] = load4<TI>(dy + (long long)mc * C + cc);
+                    rv[u][j] = dx_in ? *reinterpret_cast<const float4*>(dx_in + (long long)mc * C + cc) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
                 xv[u][j] = *reinterpret_cast<const float4*>(x + (long long)mc * C + cc);
-                rv[u][j] = dx_in ? *reinterpret_cast<const float4*>(dx_in + (long long)mc * C + cc) : make_float4(0.f, 0.f, 0.f, 0.f);
             }
+        }
+        if constexpr (SR) {
+#pragma unroll
+            for (int u = 0; u < RU; ++u)
+#pragma unroll
+                for (int j = 0; j < MAXV; ++j) {
+                    float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+                        if (tv[u][t]) {
+                            const uint2 v = raw[u][j][t];
+                            s[0] += __uint_as_float(v.x << 16);
+                            s[1] += __uint_as_float(v.x & 0xffff0000u);
+                            s[2] += __uint_as_float(v.y << 16);
+                            s[3] += __uint_as_float(v.y & 0xffff0000u);
+                        }
+                    uint2 pk = make_uint2(pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3]));
+                    if (tok[u]) pk = raw[u][j][0];                   // a token row is read, not summed (0 + -0 would lose the sign)
+                    gv[u][j] = make_float4(__uint_as_float(pk.x << 16), __uint_as_float(pk.x & 0xffff0000u), __uint_as_float(pk.y << 16),
+                                           __uint_as_float(pk.y & 0xffff0000u));
+                }
         }
 #pragma unroll
         for (int u = 0; u < RU; ++u) {
@@ -191,7 +254,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const TI* __restrict__ dy, 
                 if (c < C && rok[u]) {
                     // channels >= keep get exactly 0 (also for the pass-through residual gradient): the reference lets
                     // garbage flow there until the stage's `x * mask` kills it (nets/channel_drop.py:82); same param grads.
-                    const float4 r = rv[u][j];
+                    float4 r = rv[u][j];
+                    if constexpr (SR) {
+                        // the shortcut's gradient as sr_resid_bwd_kernel rounds it; kept out of the fma below, which adds a stored value
+                        r.x *= fr[u]; r.y *= fr[u]; r.z *= fr[u]; r.w *= fr[u];
+                        asm volatile("" : "+v"(r.x), "+v"(r.y), "+v"(r.z), "+v"(r.w));
+                    }
                     float4 o;
                     o.x = (c + 0 < kc[u]) ? (g[j].x - (s1 + z[j].x * s2)) * rs[u] + r.x : 0.f;
                     o.y = (c + 1 < kc[u]) ? (g[j].y - (s1 + z[j].y * s2)) * rs[u] + r.y : 0.f;
@@ -308,11 +376,10 @@ extern "C" int vr_ln_fwd(const float* x, const float* w, const float* b, void* y
     return VR_OK;
 }
 
-extern "C" int vr_ln_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
-                         const int32_t* keep, const float* dx_in, float* dx_out, float* dw, float* db, void* gt_out,
-                         const float* gt_scale, const int32_t* gt_keep, int32_t M, int32_t C, int32_t rows_per_sample,
-                         int32_t dy_dtype, int32_t grad_copies, vr_stream_t stream) {
-    if (!dy || !x || !w || !mean || !rstd || !dx_out || !dw || !db || M <= 0 || C <= 0 || grad_copies < 0) return VR_EINVAL;
+static int ln_bwd_launch(const void* dy, const float* x, const float* w, const float* mean, const float* rstd, const int32_t* keep,
+                         const float* dx_in, float* dx_out, float* dw, float* db, void* gt_out, const float* gt_scale,
+                         const int32_t* gt_keep, int32_t M, int32_t C, int32_t rows_per_sample, int32_t dy_dtype, int32_t grad_copies,
+                         const SrSrc* srp, vr_stream_t stream) {
     const int copies = grad_copies > 1 ? grad_copies : 1;
     if (C % 4 || C > 64 * 4 * MAXV_LIMIT) return VR_EUNSUPPORTED;
     if (dy_dtype != VR_F32 && dy_dtype != VR_BF16) return VR_EUNSUPPORTED;
@@ -322,13 +389,17 @@ extern "C" int vr_ln_bwd(const void* dy, const float* x, const float* w, const f
     const int BWD_ROWS = copies > 1 ? (M >= 8192 ? 16 : (M >= 2048 ? 8 : 4)) : (M >= 32768 ? 64 : (M >= 8192 ? 32 : (M >= 2048 ? 8 : 4)));
     dim3 grid((M + BWD_ROWS - 1) / BWD_ROWS);
     const int nv = (C + 255) / 256;
+    const SrSrc sr = srp ? *srp : SrSrc{nullptr, nullptr, nullptr, 0, 0, 0};
 #define VR_LN_BWD(NV)                                                                                                  \
-    if (dy_dtype == VR_F32)                                                                                            \
-        hipLaunchKernelGGL((ln_bwd_kernel<float, NV>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, x, w, \
-                           mean, rstd, keep, dx_in, dx_out, dw, db, (float*)gt_out, gt_scale, gt_keep, M, C, rows_per_sample, BWD_ROWS, copies, knob_xcd); \
+    if (srp)                                                                                                           \
+        hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, NV, true>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, x, \
+                           w, mean, rstd, keep, dx_in, dx_out, dw, db, (bf16_t*)gt_out, gt_scale, gt_keep, M, C, rows_per_sample, BWD_ROWS, copies, knob_xcd, sr); \
+    else if (dy_dtype == VR_F32)                                                                                       \
+        hipLaunchKernelGGL((ln_bwd_kernel<float, NV, false>), grid, dim3(256), 0, (hipStream_t)stream, (const float*)dy, x, w, \
+                           mean, rstd, keep, dx_in, dx_out, dw, db, (float*)gt_out, gt_scale, gt_keep, M, C, rows_per_sample, BWD_ROWS, copies, knob_xcd, sr); \
     else                                                                                                               \
-        hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, NV>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, x, \
-                           w, mean, rstd, keep, dx_in, dx_out, dw, db, (bf16_t*)gt_out, gt_scale, gt_keep, M, C, rows_per_sample, BWD_ROWS, copies, knob_xcd);
+        hipLaunchKernelGGL((ln_bwd_kernel<bf16_t, NV, false>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)dy, x, \
+                           w, mean, rstd, keep, dx_in, dx_out, dw, db, (bf16_t*)gt_out, gt_scale, gt_keep, M, C, rows_per_sample, BWD_ROWS, copies, knob_xcd, sr);
     switch (nv) {
         case 1: VR_LN_BWD(1) break;
         case 2: VR_LN_BWD(2) break;
@@ -340,6 +411,31 @@ extern "C" int vr_ln_bwd(const void* dy, const float* x, const float* w, const f
 #undef VR_LN_BWD
     VR_CHECK_LAUNCH();
     return VR_OK;
+}
+
+extern "C" int vr_ln_bwd(const void* dy, const float* x, const float* w, const float* mean, const float* rstd,
+                         const int32_t* keep, const float* dx_in, float* dx_out, float* dw, float* db, void* gt_out,
+                         const float* gt_scale, const int32_t* gt_keep, int32_t M, int32_t C, int32_t rows_per_sample,
+                         int32_t dy_dtype, int32_t grad_copies, vr_stream_t stream) {
+    if (!dy || !x || !w || !mean || !rstd || !dx_out || !dw || !db || M <= 0 || C <= 0 || grad_copies < 0) return VR_EINVAL;
+    return ln_bwd_launch(dy, x, w, mean, rstd, keep, dx_in, dx_out, dw, db, gt_out, gt_scale, gt_keep, M, C, rows_per_sample, dy_dtype,
+                         grad_copies, nullptr, stream);
+}
+
+extern "C" int vr_ln_bwd_sr(const void* dcol, const void* dy_tok, const float* gout, const float* x, const float* w,
+                            const float* mean, const float* rstd, const int32_t* keep, float* dx_out, float* dw, float* db,
+                            void* gt_out, const float* gt_scale, const int32_t* gt_keep, int32_t B, int32_t g, int32_t C,
+                            int32_t Cout, int32_t num_tokens, int32_t grad_copies, vr_stream_t stream) {
+    if (!dcol || !gout || !x || !w || !mean || !rstd || !dx_out || !dw || !db || B <= 0 || g <= 0 || C <= 0 || num_tokens < 0 ||
+        (num_tokens > 0 && !dy_tok) || grad_copies < 0)
+        return VR_EINVAL;
+    if ((g & 1) || C % 8 || Cout % 4 || Cout < C) return VR_EUNSUPPORTED;
+    if (((uintptr_t)dcol & 7) || ((uintptr_t)dy_tok & 7) || ((uintptr_t)gout & 15)) return VR_EALIGN;
+    const long long rows = (long long)B * (num_tokens + g * g);
+    if (rows > 0x7fffffffLL) return VR_EUNSUPPORTED;
+    const SrSrc sr{(const bf16_t*)dcol, (const bf16_t*)dy_tok, gout, g, num_tokens, Cout};
+    return ln_bwd_launch(dcol, x, w, mean, rstd, keep, nullptr, dx_out, dw, db, gt_out, gt_scale, gt_keep, (int32_t)rows, C,
+                         num_tokens + g * g, VR_BF16, grad_copies, &sr, stream);
 }
 
 extern "C" int vr_ln_grad_reduce(const vr_ln_grad_slot* slots, int32_t count, int32_t copies, vr_stream_t stream) {

@@ -270,9 +270,11 @@ __global__ __launch_bounds__(256) void softce_train_reg_kernel(const float* __re
                                                                const long long* __restrict__ sample_map, int rps,
                                                                float* __restrict__ loss_acc, TG* __restrict__ dx, int ld_grad, int R,
                                                                int K, float gscale, float loss_scale) {
+    __shared__ float wloss[4];
     const int lane = threadIdx.x & 63;
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (r >= R) return;
+    const int rr = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool live = rr < R;
+    const int r = live ? rr : R - 1;                                          // (a wave past R repeats the last row and stores nothing)
     const int s = r / rps;
     const long long trow = (sample_map ? sample_map[s] : (long long)s) * rps + (r - s * rps);
     const float* xr = x + (long long)r * K;
@@ -305,7 +307,11 @@ __global__ __launch_bounds__(256) void softce_train_reg_kernel(const float* __re
     st = wave_sum(st);
     stx = wave_sum(stx);
     const float lse = mx + __logf(se);
-    if (lane == 0) atomicAdd(loss_acc, (lse * st - stx) * loss_scale);
+    // one atomic per workgroup: the four rows' terms meet in LDS (one same-address atomic per row was 2048 of them on one word)
+    if (lane == 0) wloss[threadIdx.x >> 6] = live ? (lse * st - stx) * loss_scale : 0.f;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(loss_acc, (wloss[0] + wloss[1]) + (wloss[2] + wloss[3]));
+    if (!live) return;
     TG* dr = dx + (long long)r * ld_grad;
     const float c = st / se;
 #pragma unroll
@@ -623,7 +629,7 @@ __global__ __launch_bounds__(256) void sr_resid_bwd_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int vr_version(void) { return 1004; }
+extern "C" int vr_version(void) { return 1005; }
 
 template <typename TD> static int cast_f32(const float* src, void* dst, int64_t n, vr_stream_t stream) {
     if (!src || !dst || n <= 0) return VR_EINVAL;

@@ -31,6 +31,9 @@ class GemmArgs(ctypes.Structure):
         ("act", c_int32), ("atomic", c_int32), ("split_k", c_int32), ("rows_in", c_int32), ("n_period", c_int32), ("k_period", c_int32), ("sched", c_int32),
         ("a_map", RowMap), ("b_map", RowMap), ("c_map", RowMap), ("m_groups", c_int32),
         ("ws", c_void_p), ("ws_bytes", c_int64), ("ring", c_int32), ("k_shares", c_int32),
+        ("sr_x", c_void_p), ("keep_out", c_void_p), ("tok_src", c_void_p), ("tok_pos", c_void_p),
+        ("sr_g", c_int32), ("sr_cin", c_int32), ("sr_tokens", c_int32),
+        ("tok_rows", c_int32), ("tok_ld", c_int32), ("tok_rps", c_int32), ("tok_cols", c_int32), ("reserved0", c_int32),
     ]
 
 
@@ -86,6 +89,7 @@ SYMBOLS = {
     "vr_cast_transpose_batch": [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p],
     "vr_ln_fwd": [c_void_p] * 7 + [c_int32, c_int32, c_int32, c_float, c_int32, c_void_p],
     "vr_ln_bwd": [c_void_p] * 13 + [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
+    "vr_ln_bwd_sr": [c_void_p] * 14 + [c_int32] * 6 + [c_void_p],
     "vr_ln_grad_reduce": [ctypes.POINTER(LnGradSlot), c_int32, c_int32, c_void_p],
     "vr_attn_fwd": [c_void_p] * 4 + [c_int32] * 4 + [c_float, c_int32, c_void_p],
     "vr_attn_bwd": [c_void_p] * 7 + [c_int32] * 4 + [c_float, c_int32, c_void_p],

@@ -37,6 +37,22 @@ OVERLAP = _os.environ.get('VITRES_OVERLAP', '1') != '0'
 FUSE_LN = True
 FUSE_LN_MAXN = 256
 FUSE_LN_FWD_MAXK = 4096
+# The spatial-reduction block's glue passes inside the kernels that touch the same rows anyway, same bits:
+#   forward: the conv GEMM's epilogue adds the pooled shortcut (2 x 2 mean of x), applies the outer mask last and stores the token-row
+#     copies that the token GEMM adds as its residual (no vr_sr_resid, no vr_mask_rows); the patch-embedding GEMM stores the token
+#     rows of the embedding (no vr_embed_cls);
+#   backward (vr_ln_bwd_sr): the LayerNorm backward gathers its dy from the conv data gradient (col2im) and its dx_in from the
+#     incoming gradient (the pooled shortcut's backward) -- no vr_sr_col2im, no vr_sr_resid_bwd, two written-once tensors less.
+# FUSE_SR = False (test aid): the separate launches, the paths the folds are tested against.
+FUSE_SR = True
+
+
+def _fold_gemm(x, dt):
+    """The forward folds of FUSE_SR live in the 16-bit forward GEMM kernels (vr_gemm_args.sr_x / keep_out / tok_src): the fp32 parity
+    mode keeps the separate launches."""
+    return FUSE_SR and x.is_cuda and K.is_fast16(dt)
+
+
 # LayerNorm weight / bias gradients: the workgroups of a LayerNorm backward add their column sums into LN_COPIES rows of
 # partial sums (grads["<weight key>.part"], [2, LN_COPIES, C], kept zero between backwards) instead of all of them into
 # the same 2C addresses; flush_ln_grads() folds the rows of every LayerNorm of a backward part in one launch.  vr_ln_bwd at
@@ -406,15 +422,27 @@ def sr_fwd(x, p, cfg, embed_keep, new_keep, save, pre=None):
     Co = cfg["cout"]
     dt = cfg["dtype"]
     y, mean, rstd = pre if pre is not None else K.ln_fwd(x, p["nw"], p["nb"], embed_keep, Ni, cfg["eps"], dt)
-    out = K.sr_resid(x, B, g, C, Co, T)
-    col = K.sr_im2col(y, B, g, C, T)
-    K.gemm(col, p["reduce"].w_c, out, M=B * go * go, N=Co, K=9 * C, lda=9 * C, ldb=p["reduce"].ld, ldc=Co,
-           bias=p["reduce"].b, pos=p["pos"], resid=out, rows_in=go * go, c_map=(go * go, No, T), keep_k=embed_keep,
-           k_period=C)
-    K.gemm(y, p["token"].w_c, out, M=B * T, N=Co, K=C, lda=C, ldb=p["token"].ld, ldc=Co, bias=p["token"].b, resid=out,
-           rows_in=T, a_map=(T, Ni, 0), c_map=(T, No, 0))
-    if new_keep is not None:
-        K.mask_rows(out, new_keep, No)
+    if _fold_gemm(x, dt) and C % 8 == 0 and Co % 8 == 0 and T > 0:
+        # the pooled shortcut, the copied token rows and the outer mask inside the two GEMM launches: no vr_sr_resid, no vr_mask_rows.
+        # The conv GEMM adds the 2 x 2 mean of x in its epilogue, masks last and stores the (masked) token-row copies beside its tiles;
+        # the token GEMM then adds them as its residual, exactly as before, and masks its own term (0 + 0 beyond new_keep).
+        out = torch.empty((B, No, Co), dtype=torch.float32, device=x.device)
+        col = K.sr_im2col(y, B, g, C, T)
+        K.gemm(col, p["reduce"].w_c, out, M=B * go * go, N=Co, K=9 * C, lda=9 * C, ldb=p["reduce"].ld, ldc=Co,
+               bias=p["reduce"].b, pos=p["pos"], rows_in=go * go, c_map=(go * go, No, T), keep_k=embed_keep, k_period=C,
+               sr_pool=(x, g, T), keep_out=new_keep, tok_rows=(x, None, T, C, Ni, C))
+        K.gemm(y, p["token"].w_c, out, M=B * T, N=Co, K=C, lda=C, ldb=p["token"].ld, ldc=Co, bias=p["token"].b, resid=out,
+               rows_in=T, a_map=(T, Ni, 0), c_map=(T, No, 0), keep_n=new_keep)
+    else:
+        out = K.sr_resid(x, B, g, C, Co, T)
+        col = K.sr_im2col(y, B, g, C, T)
+        K.gemm(col, p["reduce"].w_c, out, M=B * go * go, N=Co, K=9 * C, lda=9 * C, ldb=p["reduce"].ld, ldc=Co,
+               bias=p["reduce"].b, pos=p["pos"], resid=out, rows_in=go * go, c_map=(go * go, No, T), keep_k=embed_keep,
+               k_period=C)
+        K.gemm(y, p["token"].w_c, out, M=B * T, N=Co, K=C, lda=C, ldb=p["token"].ld, ldc=Co, bias=p["token"].b, resid=out,
+               rows_in=T, a_map=(T, Ni, 0), c_map=(T, No, 0))
+        if new_keep is not None:
+            K.mask_rows(out, new_keep, No)
     saved = (x, mean, rstd, y, col) if save else None
     return out, saved
 
@@ -447,12 +475,17 @@ def sr_bwd(gout, saved, p, grads, cfg, embed_keep, new_keep, gt=None, next_cast=
         wgrads()
     dcol = torch.empty((B * P, 9 * C), dtype=dt, device=x.device)
     linear_dgrad(gt, p["reduce"], dcol, B * P, 9 * C, Co, Co, 9 * C, a_map=(P, No, T), rows_in=P)
-    dy = torch.empty((B, Ni, C), dtype=dt, device=x.device)
-    K.sr_col2im(dcol, dy, B, g, C, T)
-    linear_dgrad(gt, p["token"], dy, B * T, C, Co, Co, C, a_map=(T, No, 0), c_map=(T, Ni, 0), rows_in=T)
-    gres = K.sr_resid_bwd(gout, B, g, C, Co, T)
     dw, db, cp = _ln_dst(grads, "nw", "nb")
-    out = K.ln_bwd(dy, x, p["nw"], mean, rstd, embed_keep, Ni, gres, dw, db, next_cast=next_cast, copies=cp)
+    if FUSE_SR and x.is_cuda and dt == torch.bfloat16 and C % 8 == 0 and Co % 4 == 0:
+        dy_tok = torch.empty((B * T, C), dtype=dt, device=x.device)
+        linear_dgrad(gt, p["token"], dy_tok, B * T, C, Co, Co, C, a_map=(T, No, 0), rows_in=T)
+        out = K.ln_bwd_sr(dcol, dy_tok, gout, x, p["nw"], mean, rstd, embed_keep, g, T, dw, db, next_cast=next_cast, copies=cp)
+    else:
+        dy = torch.empty((B, Ni, C), dtype=dt, device=x.device)
+        K.sr_col2im(dcol, dy, B, g, C, T)
+        linear_dgrad(gt, p["token"], dy, B * T, C, Co, Co, C, a_map=(T, No, 0), c_map=(T, Ni, 0), rows_in=T)
+        gres = K.sr_resid_bwd(gout, B, g, C, Co, T)
+        out = K.ln_bwd(dy, x, p["nw"], mean, rstd, embed_keep, Ni, gres, dw, db, next_cast=next_cast, copies=cp)
     if _overlap(gout):
         join_side_lagged()                 # (a full join here stalled the main chain ~200 us behind the conv weight gradient)
     return out
@@ -472,9 +505,14 @@ def embed0_fwd(img, p, cfg, keep, save, sample_map=None, col=None):
     if col is None:
         col = K.im2col_patch(img, cfg["patch"], ldk, dt, sample_map=sample_map)
     x = torch.empty((B, N, C), dtype=torch.float32, device=img.device)
-    K.gemm(col, p["proj"].w_c, x, M=B * P, N=C, K=ldk, lda=ldk, ldb=ldk, ldc=C, bias=p["proj"].b, pos=p["pos"][0, T:],
-           keep_n=keep, rows_in=P, c_map=(P, N, T))
-    K.embed_cls(p["tokens"], p["pos"], x, keep, T)
+    if _fold_gemm(x, dt) and C % 8 == 0 and T > 0:
+        # the launch's workgroups that hold a sample's first patch row also store its token rows (tokens + pos, masked): no vr_embed_cls
+        K.gemm(col, p["proj"].w_c, x, M=B * P, N=C, K=ldk, lda=ldk, ldb=ldk, ldc=C, bias=p["proj"].b, pos=p["pos"][0, T:],
+               keep_n=keep, rows_in=P, c_map=(P, N, T), tok_rows=(p["tokens"], p["pos"], T, C, 0, C))
+    else:
+        K.gemm(col, p["proj"].w_c, x, M=B * P, N=C, K=ldk, lda=ldk, ldb=ldk, ldc=C, bias=p["proj"].b, pos=p["pos"][0, T:],
+               keep_n=keep, rows_in=P, c_map=(P, N, T))
+        K.embed_cls(p["tokens"], p["pos"], x, keep, T)
     return x, ((col,) if save else None)
 
 

@@ -120,8 +120,20 @@ DBG_POISON = False
 def _gemm_args(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=False, out2=None, bias=None, pos=None,
                scale=None, keep_n=None, resid=None, dact_u=None, ldu=0, act=0, atomic=False, split_k=1, rows_in=0,
                a_map=None, b_map=None, c_map=None, bias_grad=None, keep_k=None, n_period=0, k_period=0, sched=0, ws="auto",
-               ring=0, k_shares=0, m_groups=None):
+               ring=0, k_shares=0, m_groups=None, sr_pool=None, keep_out=None, tok_rows=None):
+    """sr_pool = (x [B, T + g*g, Cin] fp32, g, T): the pooled shortcut of a spatial-reduction block added where resid would be;
+    keep_out: the outer prefix mask, applied last; tok_rows = (src, pos or None, T, ld, rows per sample or 0, cols): the launch also
+    writes the T token rows of every sample (vr_gemm_args.sr_x / keep_out / tok_src)."""
     args = GemmArgs()
+    if sr_pool is not None:
+        sx, sg, st = sr_pool
+        assert sx.dtype == torch.float32 and sx.is_contiguous() and sx.shape[1] == st + sg * sg
+        args.sr_x, args.sr_g, args.sr_cin, args.sr_tokens = _p(sx), sg, sx.shape[-1], st
+    args.keep_out = _p(keep_out)
+    if tok_rows is not None:
+        src, tpos, tn, tld, trps, tcols = tok_rows
+        assert src.dtype == torch.float32 and (tpos is None or tpos.dtype == torch.float32)
+        args.tok_src, args.tok_pos, args.tok_rows, args.tok_ld, args.tok_rps, args.tok_cols = _p(src), _p(tpos), tn, tld, trps, tcols
     if isinstance(ws, str):         # "auto": the role's workspace wherever the K-split kernels (gemm_ntk.hip) could be chosen
         ws = _workspace(a.device) if (not a_trans and is_fast16(a.dtype) and a.is_cuda and K >= 512 and k_shares != 1) else None
     if ws is not None:
@@ -267,14 +279,14 @@ def gemm_ln_bwd(du, wt, x, ln_w, mean, rstd, ln_keep, dx_in, dw, db, next_cast=N
 def gemm(a, b, out, *, M, N, K, lda, ldb, ldc, a_trans=False, b_trans=False, out2=None, bias=None, pos=None,
          scale=None, keep_n=None, resid=None, dact_u=None, ldu=0, act=0, atomic=False, split_k=1, rows_in=0,
          a_map=None, b_map=None, c_map=None, bias_grad=None, keep_k=None, n_period=0, k_period=0, sched=0, ws="auto",
-         ring=0, k_shares=0, m_groups=None):
+         ring=0, k_shares=0, m_groups=None, sr_pool=None, keep_out=None, tok_rows=None):
     """out[M,N] = epilogue(a[M,K] @ b[N,K]^T) -- see vr_gemm in include/vitres_hip.h.  ws: K-split workspace (a uint8 tensor),
-    None, or "auto" = the current role's (see _workspace)."""
+    None, or "auto" = the current role's (see _workspace).  sr_pool / keep_out / tok_rows: see _gemm_args."""
     args = _gemm_args(a, b, out, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc, a_trans=a_trans, b_trans=b_trans, out2=out2,
                       bias=bias, pos=pos, scale=scale, keep_n=keep_n, resid=resid, dact_u=dact_u, ldu=ldu, act=act,
                       atomic=atomic, split_k=split_k, rows_in=rows_in, a_map=a_map, b_map=b_map, c_map=c_map,
                       bias_grad=bias_grad, keep_k=keep_k, n_period=n_period, k_period=k_period, sched=sched, ws=ws,
-                      ring=ring, k_shares=k_shares, m_groups=m_groups)
+                      ring=ring, k_shares=k_shares, m_groups=m_groups, sr_pool=sr_pool, keep_out=keep_out, tok_rows=tok_rows)
     if DBG_POISON and (args.sched & SKIP_WRITES_BIT) and keep_n is not None and not a_trans and resid is None and \
             is_fast16(out.dtype):
         out.fill_(float("nan"))
@@ -514,6 +526,21 @@ def ln_bwd(dy, x, w, mean, rstd, keep, rows_per_sample, dx_in, dw, db, next_cast
     sc, kp = next_cast if next_cast is not None else (None, None)
     _lib.check(_lib.lib().vr_ln_bwd(_p(dy), _p(x), _p(w), _p(mean), _p(rstd), _p(keep), _p(dx_in), _p(dx), _p(dw), _p(db),
                                     _p(gt), _p(sc), _p(kp), M, C, rows_per_sample, _dt(dy), copies, _stream()), "vr_ln_bwd")
+    return dx if next_cast is None else (dx, gt)
+
+
+def ln_bwd_sr(dcol, dy_tok, gout, x, w, mean, rstd, keep, g, num_tokens, dw, db, next_cast=None, copies=1):
+    """ln_bwd of a spatial-reduction block's LayerNorm with col2im (patch rows of dy from dcol), the token rows of dy (dy_tok
+    [B * num_tokens, C]) and the pooled shortcut's gradient (dx_in from gout [B, No, Cout]) read in place (vr_ln_bwd_sr; bf16)."""
+    B, Ni, C = x.shape
+    assert Ni == num_tokens + g * g and dcol.dtype == torch.bfloat16 and dy_tok.dtype == torch.bfloat16
+    assert dcol.numel() == B * (g // 2) ** 2 * 9 * C and dy_tok.numel() == B * num_tokens * C and gout.shape[0] == B
+    dx = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    gt = torch.empty(x.shape, dtype=dcol.dtype, device=x.device) if next_cast is not None else None
+    sc, kp = next_cast if next_cast is not None else (None, None)
+    _lib.check(_lib.lib().vr_ln_bwd_sr(_p(dcol), _p(dy_tok), _p(gout), _p(x), _p(w), _p(mean), _p(rstd), _p(keep), _p(dx), _p(dw),
+                                       _p(db), _p(gt), _p(sc), _p(kp), B, g, C, gout.shape[-1], num_tokens, copies, _stream()),
+               "vr_ln_bwd_sr")
     return dx if next_cast is None else (dx, gt)
 
 
