@@ -571,6 +571,46 @@ int vr_mixup_u8_erase(const uint8_t* samples, float* out, const int64_t* labels,
                       const float* mean, const float* std, const vr_erase_args* erase, vr_stream_t stream);
 
 /*
+ * The geometric head of the input chain on the device: crop, resize, window and mirror of a uint8 batch in one pass (timm's
+ * RandomResizedCropAndInterpolation + RandomHorizontalFlip in training, Resize + CenterCrop in evaluation; datasets.py:117-119 hands
+ * both to timm's create_transform).  The loader only decodes and pads its images into a uint8 canvas [B,C,Hs,Ws]; the output is the
+ * uint8 [B,C,So_h,So_w] batch vr_normalize_u8 / vr_token_mix_u8 / vr_mixup_u8 take.  Per sample and channel, bit for bit (PIL 12):
+ *     PIL.Image.crop((x0, y0, x0+w, y0+h)).resize((ow, oh), filter).crop((wx, wy, wx+So_w, wy+So_h)) [.transpose(FLIP_LEFT_RIGHT) if flip]
+ * i.e. PIL's 8-bit resample: a horizontal pass over the source rows the vertical pass touches, rounded and clipped to uint8, then
+ * the vertical pass.  Per axis, in double precision and one rounding per operator (no fused multiply-add), in = the crop's size,
+ * out = ow / oh:  scale = in / out, fs = max(scale, 1), support = S_f * fs (S_f = 1 bilinear, 2 bicubic), ss = 1 / fs; output index
+ * xx has center = (xx + 0.5) * scale, taps x in [max(0, (int)(center - support + 0.5)), min(in, (int)(center + support + 0.5))) with
+ * weight f((x - center + 0.5) * ss) divided by the taps' sum; f = 1 - |t| (|t| < 1), or the a = -0.5 cubic ((a+2)|t| - (a+3)) t^2 + 1
+ * (|t| < 1), (((|t| - 5)|t| + 8)|t| - 4) a (|t| < 2); fixed point k = (int)(w * 2^22 +- 0.5), the sign following w; int32 sums that
+ * start at 2^21; result clamp(sum >> 22, 0, 255).  The supports are clipped to the CROP, not to the canvas (torchvision's
+ * resized_crop).  Only the window's pixels and the source rows they need are computed.
+ *   random-resized crop: ow = oh = S, wx = wy = 0;   evaluation: box = the image, (ow, oh) = the resized size, window = the centre crop.
+ * `boxes` is a DEVICE array read at run time: a captured launch follows boxes rewritten in place, and the entry point does no
+ * per-batch host work.  The coefficients are computed inside the kernel (fp64), so vr_resample_ws_bytes is 0 and workspace may be NULL.
+ * One workgroup per (sample, band of output rows); the band height (vr_resample_band_rows) is the tallest, up to 32 rows, whose LDS
+ * image -- coefficient tables, the uint8 intermediate of the band's source rows, one staged source row per wave -- stays within 64 KiB
+ * for the launch's worst possible scale, Hs / So_h and Ws / So_w (a box inside the canvas and a window inside (ow, oh) cannot
+ * exceed them).  VR_EUNSUPPORTED when not even a one-row band fits, when So_w % 4 or Ws % 4, or B > 65535; VR_EINVAL: a null pointer,
+ * src == out, a non-positive size, C outside 1..4, filter not 2 / 3; VR_EALIGN: src, out or boxes not 4-byte aligned.  The caller
+ * guarantees w, h >= 1, the box inside Hs x Ws and the window inside (ow, oh) (vitres.kernels.resample_u8 checks its host copy); the
+ * kernel clamps a box that breaks this into range, so it selects other pixels and addresses nothing outside the buffers.
+ */
+typedef struct vr_resample_box {
+    int32_t x0, y0, w, h;      /* source box inside this sample's canvas (the crop); w, h >= 1                       */
+    int32_t ow, oh;            /* size of the VIRTUAL resized image the box is resampled to                          */
+    int32_t wx, wy;            /* origin of the output window inside that virtual image (0,0 for a plain crop-resize) */
+    int32_t flip;              /* != 0: the written window is mirrored left-right                                     */
+    int32_t reserved[3];
+} vr_resample_box;             /* 48 bytes */
+int vr_resample_u8(const uint8_t* src /* [B,C,Hs,Ws] */, const vr_resample_box* boxes /* device, [B] */,
+                   uint8_t* out /* [B,C,So_h,So_w] */, int32_t B, int32_t C, int32_t Hs, int32_t Ws,
+                   int32_t So_h, int32_t So_w, int32_t filter /* 2 bilinear, 3 bicubic: PIL's numbers */,
+                   void* workspace, size_t ws_bytes, vr_stream_t stream);
+size_t vr_resample_ws_bytes(int32_t B, int32_t So_h, int32_t So_w);   /* 0: the kernel needs none */
+/* output rows per workgroup of that launch (> 0), or the negative code vr_resample_u8 would return for these dimensions */
+int vr_resample_band_rows(int32_t C, int32_t Hs, int32_t Ws, int32_t So_h, int32_t So_w, int32_t filter);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

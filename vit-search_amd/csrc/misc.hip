@@ -629,7 +629,7 @@ __global__ __launch_bounds__(256) void sr_resid_bwd_kernel(const float* __restri
 
 }  // namespace
 
-extern "C" int vr_version(void) { return 1005; }
+extern "C" int vr_version(void) { return 1006; }
 
 template <typename TD> static int cast_f32(const float* src, void* dst, int64_t n, vr_stream_t stream) {
     if (!src || !dst || n <= 0) return VR_EINVAL;

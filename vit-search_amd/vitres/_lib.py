@@ -67,6 +67,14 @@ class EraseArgs(ctypes.Structure):
 VR_ERASE_CONST, VR_ERASE_RAND, VR_ERASE_PIXEL = 0, 1, 2
 
 
+class ResampleBox(ctypes.Structure):
+    _fields_ = [("x0", c_int32), ("y0", c_int32), ("w", c_int32), ("h", c_int32), ("ow", c_int32), ("oh", c_int32),
+                ("wx", c_int32), ("wy", c_int32), ("flip", c_int32), ("reserved", c_int32 * 3)]
+
+
+VR_BILINEAR, VR_BICUBIC = 2, 3            # PIL's filter numbers
+
+
 # name -> argtypes ; every entry point returns int.  Must list every symbol of include/vitres_hip.h
 SYMBOLS = {
     "vr_version": [],
@@ -115,6 +123,8 @@ SYMBOLS = {
     "vr_token_mix_u8_erase": [c_void_p] * 6 + [c_int32] * 11 + [c_float] * 6 + [c_void_p, c_void_p, ctypes.POINTER(EraseArgs),
                                                                                c_void_p],
     "vr_mixup_u8_erase": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p, c_void_p, ctypes.POINTER(EraseArgs), c_void_p],
+    "vr_resample_u8": [c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, ctypes.c_size_t, c_void_p],
+    "vr_resample_band_rows": [c_int32] * 6,
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],
@@ -142,6 +152,11 @@ SYMBOLS = {
     "vr_conv3x3_res_patch": [c_void_p] * 4 + [c_int32] * 7 + [c_void_p],
 }
 
+# the entry points that do not return int: name -> (argtypes, restype)
+OTHER_SYMBOLS = {
+    "vr_resample_ws_bytes": ([c_int32, c_int32, c_int32], ctypes.c_size_t),
+}
+
 _lib = None
 
 
@@ -161,6 +176,12 @@ def lib():
                 raise RuntimeError("libvitres_hip.so does not export %s" % name) from e
             fn.argtypes = argtypes
             fn.restype = ctypes.c_int
+        for name, (argtypes, restype) in OTHER_SYMBOLS.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError as e:
+                raise RuntimeError("libvitres_hip.so does not export %s" % name) from e
+            fn.argtypes, fn.restype = argtypes, restype
         _lib = L
     return _lib
 

@@ -7,11 +7,17 @@ training, the `vr_token_mix_u8` pass of `SwitchTokenMix(input_norm=...)` -- make
   DevicePrefetchLoader   timm's PrefetchLoader: host batches, copied one batch ahead on a side stream.
   ResidentU8Batches      a hold-out set kept on the device as uint8 (a quarter of its fp32 size), re-iterable: what
                          evo_eval.score_candidate / score_population and engine.evaluate take as `batches`.
+  pad_collate_u8         a collate function for decoded images of different sizes: one zero-padded uint8 canvas per batch.
+  DeviceCropLoader       canvases in, cropped / resized / mirrored uint8 [B,3,S,S] device batches out (vr_resample_u8 with the boxes
+                         of a vitres.resized_crop transform): what the two classes above, SwitchTokenMix(input_norm=) and
+                         Mixup(input_norm=) take.
 
-What is not here: decoding and the geometric / colour augmentations stay with the loader that produces the uint8 batches.  Random
+What is not here: decoding and the colour augmentations (RandAugment, ColorJitter -- they work on the cropped image, so a recipe that
+uses them still crops on the host) stay with the loader that produces the uint8 batches.  Random
 erasing, which timm applies to the normalised image, cannot happen there any more: `erase=` (a vitres.random_erasing.RandomErasing)
 folds it into the normalising pass -- here with normalize=True, in the mix (`SwitchTokenMix(..., erase=)`, `Mixup(..., erase=)`) in training.
 """
+import numpy as np
 import torch
 
 from . import kernels as K
@@ -103,3 +109,83 @@ class ResidentU8Batches:
             out = self._bufs[self._turn][:u8.shape[0]]
             self._turn ^= 1
             yield K.normalize_u8(u8, *self.norm, out=out), self.targets[lo:lo + self.batch_size]
+
+
+def pad_collate_u8(samples):
+    """Collate a list of (HWC uint8 array, label) -- decoded images of any sizes, one channel count -- into
+    (canvas uint8 [B,C,Hs,Ws], sizes int32 [B,2] of (h, w), labels int64 [B]): every image sits in the top-left corner of its
+    canvas plane, the rest is zero; Hs and Ws are the batch maxima rounded up to a multiple of 4 (vr_resample_u8 reads rows as
+    dwords).  What a DataLoader(collate_fn=pad_collate_u8) hands to DeviceCropLoader."""
+    if not samples:
+        raise ValueError("pad_collate_u8: an empty batch")
+    images = [np.asarray(img) for img, _ in samples]
+    for img in images:
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != images[0].shape[2] or 0 in img.shape:
+            raise TypeError("pad_collate_u8 takes non-empty HWC uint8 arrays of one channel count, got %s %s" % (img.dtype, img.shape))
+    sizes = np.array([img.shape[:2] for img in images], dtype=np.int32)
+    Hs, Ws = ((int(v) + 3) // 4 * 4 for v in sizes.max(axis=0))
+    canvas = np.zeros((len(images), images[0].shape[2], Hs, Ws), dtype=np.uint8)
+    for b, img in enumerate(images):
+        canvas[b, :, :img.shape[0], :img.shape[1]] = img.transpose(2, 0, 1)
+    labels = torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
+    return torch.from_numpy(canvas), torch.from_numpy(sizes), labels
+
+
+class DeviceCropLoader:
+    """Over a loader of (canvas uint8 [B,C,Hs,Ws], sizes [B,2], labels) host batches (pad_collate_u8): yields
+    (uint8 [B,C,S,S] on `device`, labels on `device`), the canvas cropped, resized and mirrored by vr_resample_u8 with the boxes
+    `transform.draw(sizes)` makes (a vitres.resized_crop.RandomResizedCrop or ResizeCenterCrop: .draw, .size, .filter).  The canvas,
+    the box table and the labels are copied one batch ahead on a side stream (the DevicePrefetchLoader pattern; pinned host batches
+    make the copies asynchronous); the boxes are drawn, and checked against the canvas, in the loader's order when a batch is
+    uploaded.  The output is what DevicePrefetchLoader, SwitchTokenMix(input_norm=), Mixup(input_norm=) and ResidentU8Batches take;
+    nothing is normalised here.  __len__, .sampler and .dataset are the wrapped loader's."""
+
+    def __init__(self, loader, transform, device):
+        self.loader, self.transform, self.device = loader, transform, torch.device(device)
+
+    def __len__(self):
+        return len(self.loader)
+
+    @property
+    def sampler(self):
+        return self.loader.sampler
+
+    @property
+    def dataset(self):
+        return self.loader.dataset
+
+    def _upload(self, side, canvas, sizes, labels):
+        if canvas.dtype != torch.uint8 or canvas.dim() != 4:
+            raise TypeError("DeviceCropLoader takes uint8 [B,C,Hs,Ws] canvases (pad_collate_u8), got %s %s" % (canvas.dtype,
+                                                                                                              tuple(canvas.shape)))
+        B, _, Hs, Ws = canvas.shape
+        sizes = np.asarray(sizes, dtype=np.int64)
+        if sizes.shape != (B, 2) or (sizes[:, 0] > Hs).any() or (sizes[:, 1] > Ws).any():
+            raise ValueError("DeviceCropLoader: sizes must hold one (h, w) inside the %d x %d canvas per sample" % (Hs, Ws))
+        table = K.check_resample_boxes(self.transform.draw(sizes), B, Hs, Ws, self.transform.size)
+        host = torch.empty(table.shape, dtype=torch.int32, pin_memory=side is not None)
+        host.numpy()[...] = table
+        if side is None:                      # (not a GPU: nothing to overlap; the kernel itself has no CPU form)
+            return canvas.to(self.device), host.to(self.device), labels.to(self.device), None
+        with torch.cuda.stream(side):
+            return (canvas.to(self.device, non_blocking=True), host.to(self.device, non_blocking=True),
+                    labels.to(self.device, non_blocking=True), side.record_event())
+
+    def __iter__(self):
+        side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
+        ahead = None
+        for canvas, sizes, labels in self.loader:
+            nxt = self._upload(side, canvas, sizes, labels)
+            if ahead is not None:
+                yield self._hand_over(*ahead)
+            ahead = nxt
+        if ahead is not None:
+            yield self._hand_over(*ahead)
+
+    def _hand_over(self, canvas, table, labels, copied):
+        if copied is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(copied)
+            for t in (canvas, table, labels):  # (allocated on the side stream, used on this one)
+                t.record_stream(cur)
+        return K.resample_u8(canvas, table, self.transform.size, self.transform.filter), labels

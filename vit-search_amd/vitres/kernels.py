@@ -1121,3 +1121,90 @@ def token_mix_u8_erase(x, labels, draw, patch_len, num_classes, on, off, norm, e
         x1, f32(draw["lam_patch"]), f32(1. - draw["lam_patch"]), f32(draw["lam_img"]), f32(1. - draw["lam_img"]), f32(on), f32(off),
         norm[0], norm[1], ctypes.byref(ea), _stream()), what)
     return out, targets, patch_targets
+
+
+# ---- crop + resize + window + mirror of uint8 batches (vr_resample_u8; vitres/resized_crop.py draws the boxes) ---------------------------
+RESAMPLE_FILTERS = {"bilinear": _lib.VR_BILINEAR, "bicubic": _lib.VR_BICUBIC, _lib.VR_BILINEAR: _lib.VR_BILINEAR,
+                    _lib.VR_BICUBIC: _lib.VR_BICUBIC}
+# one row of the device table (vr_resample_box of include/vitres_hip.h, 48 bytes = 12 int32)
+RESAMPLE_BOX_FIELDS = ("x0", "y0", "w", "h", "ow", "oh", "wx", "wy", "flip")
+RESAMPLE_BOX_INTS = ctypes.sizeof(_lib.ResampleBox) // 4
+assert RESAMPLE_BOX_INTS == 12
+
+
+def _out_size(out_size):
+    So_h, So_w = (out_size, out_size) if isinstance(out_size, int) else out_size
+    return int(So_h), int(So_w)
+
+
+def _resample_filter(filter):
+    if filter not in RESAMPLE_FILTERS:
+        raise ValueError("resample filter must be 'bilinear' (2) or 'bicubic' (3), got %r" % (filter,))
+    return RESAMPLE_FILTERS[filter]
+
+
+def resample_boxes(B):
+    """A zeroed host table int32 [B, 12]: columns RESAMPLE_BOX_FIELDS, then three reserved words."""
+    return np.zeros((B, RESAMPLE_BOX_INTS), dtype=np.int32)
+
+
+def check_resample_boxes(boxes, B, Hs, Ws, out_size, what="vr_resample_u8"):
+    """boxes as a contiguous int32 [B, 12] array (9 columns are padded with the reserved words) with w, h >= 1, every box inside the
+    Hs x Ws canvas and every window inside its (ow, oh).  The device cannot report a bad row, so the host copy is what is checked:
+    RuntimeError VR_EINVAL, before anything is launched."""
+    So_h, So_w = _out_size(out_size)
+    boxes = np.asarray(boxes)
+    if boxes.ndim != 2 or boxes.shape[0] != B or boxes.shape[1] not in (len(RESAMPLE_BOX_FIELDS), RESAMPLE_BOX_INTS):
+        raise ValueError("%s: the box table has shape %s, expected (%d, %d)" % (what, boxes.shape, B, RESAMPLE_BOX_INTS))
+    table = resample_boxes(B)
+    table[:, :boxes.shape[1]] = boxes
+    x0, y0, w, h, ow, oh, wx, wy = (table[:, i].astype(np.int64) for i in range(8))
+    bad = ((w < 1) | (h < 1) | (x0 < 0) | (y0 < 0) | (x0 + w > Ws) | (y0 + h > Hs)
+           | (wx < 0) | (wy < 0) | (wx + So_w > ow) | (wy + So_h > oh))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise RuntimeError("%s failed: %s: sample %d: the box x0=%d y0=%d w=%d h=%d must lie inside the %d x %d canvas and the %d x %d "
+                           "window at (%d, %d) inside the resized %d x %d image" % (what, _lib._ERR[-1], i, x0[i], y0[i], w[i], h[i], Hs,
+                                                                                    Ws, So_h, So_w, wy[i], wx[i], oh[i], ow[i]))
+    return table
+
+
+def resample_band_rows(C, Hs, Ws, out_size, filter):
+    """Output rows one workgroup of that vr_resample_u8 launch computes (vr_resample_band_rows); RuntimeError where the launch would
+    be refused (VR_EUNSUPPORTED: not even a one-row band fits the LDS budget at the launch's worst scale)."""
+    So_h, So_w = _out_size(out_size)
+    rc = _lib.lib().vr_resample_band_rows(C, Hs, Ws, So_h, So_w, _resample_filter(filter))
+    if rc <= 0:
+        _lib.check(rc, "vr_resample_band_rows")
+    return rc
+
+
+def resample_u8(src, boxes, out_size, filter, out=None):
+    """vr_resample_u8: per sample and channel, bit for bit,
+        PIL crop((x0, y0, x0+w, y0+h)).resize((ow, oh), filter).crop((wx, wy, wx+So_w, wy+So_h)) [mirrored left-right if flip]
+    of the uint8 canvas batch src [B,C,Hs,Ws] (Ws % 4 == 0) into uint8 [B,C,So_h,So_w] (So_w % 4 == 0).  boxes: a host int array
+    [B, 9 or 12] (columns RESAMPLE_BOX_FIELDS) -- checked, then uploaded from pinned memory on the current stream without a host
+    wait -- or an int32 [B, 12] DEVICE tensor the caller has checked (check_resample_boxes) and may rewrite in place between replays
+    of a captured launch.  out_size: S or (So_h, So_w); filter: 'bilinear' / 'bicubic' or PIL's 2 / 3; out: a preallocated result."""
+    if src.dtype != torch.uint8 or src.dim() != 4:
+        raise TypeError("resample_u8: a uint8 [B,C,Hs,Ws] tensor expected, got %s %s" % (src.dtype, tuple(src.shape)))
+    B, C, Hs, Ws = src.shape
+    So_h, So_w = _out_size(out_size)
+    code = _resample_filter(filter)
+    _p(src)
+    if isinstance(boxes, torch.Tensor):
+        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, RESAMPLE_BOX_INTS) or not boxes.is_contiguous() \
+                or boxes.device != src.device:
+            raise ValueError("resample_u8: a device box table must be a contiguous int32 [%d, %d] tensor on %s" % (
+                B, RESAMPLE_BOX_INTS, src.device))
+        table = boxes
+    else:
+        table = _upload_i32(check_resample_boxes(boxes, B, Hs, Ws, (So_h, So_w)), src.device)
+    src = src.contiguous()
+    if out is None:
+        out = torch.empty((B, C, So_h, So_w), dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, C, So_h, So_w) or not out.is_contiguous() or out.device != src.device:
+        raise ValueError("resample_u8: out must be a contiguous uint8 tensor of shape %s on %s" % ((B, C, So_h, So_w), src.device))
+    _lib.check(_lib.lib().vr_resample_u8(_p(src), _p(table), _p(out), B, C, Hs, Ws, So_h, So_w, code, None, 0, _stream()),
+               "vr_resample_u8")
+    return out
