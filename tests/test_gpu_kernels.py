@@ -1,7 +1,7 @@
 """Unit parity of every HIP kernel (through the C ABI) against the torch statement of its semantics
 (tests/emu_kernels.py) on seeded inputs.  fp32 kernels: ~1e-5; bf16 kernels: bf16 rounding of the outputs.
-Per-element derived bounds live in the four ref64 suites: attn_ref64 / test_gpu_attention, rowstat_ref64 / test_gpu_rowstat, stem_ref64 / test_gpu_stem,
-gemm_ref64 / test_gpu_gemm."""
+Per-element derived bounds and bit-exact contracts live in the five ref64 suites: attn_ref64 / test_gpu_attention, rowstat_ref64 /
+test_gpu_rowstat, stem_ref64 / test_gpu_stem, gemm_ref64 / test_gpu_gemm and glue_ref64 / test_gpu_glue (the small kernels of misc.hip)."""
 import numpy as np
 import pytest
 import torch
