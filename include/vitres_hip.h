@@ -611,6 +611,69 @@ size_t vr_resample_ws_bytes(int32_t B, int32_t So_h, int32_t So_w);   /* 0: the 
 int vr_resample_band_rows(int32_t C, int32_t Hs, int32_t Ws, int32_t So_h, int32_t So_w, int32_t filter);
 
 /*
+ * RandAugment on the device: the stage between vr_resample_u8 and the normalising / mixing passes (timm's create_transform runs
+ * crop -> flip -> RandAugment -> ToTensor -> Normalize -> RandomErasing; the recipes train with --aa rand-m9-mstd0.5-inc1).  src and
+ * out are uint8 [B,3,H,W]; `ops` holds `layers` records per sample, applied in order, layer k + 1 on layer k's output (its
+ * whole-image statistics included).  Eleven op kinds cover timm's fifteen ops; every result is, bit for bit, what PIL 12 makes of
+ * the HWC RGB image:
+ *   VR_RA_IDENTITY      drawn but not applied; costs nothing beyond getting src into out.
+ *   per-channel tables  out = lut[in]:
+ *     INVERT            255 - i                                                        (ImageOps.invert)
+ *     POSTERIZE         i & ~(2^(8 - iarg) - 1), iarg = bits kept, 0..7                (ImageOps.posterize; 8 is identity)
+ *     SOLARIZE          i < iarg ? i : 255 - i, iarg = threshold 0..256                (ImageOps.solarize)
+ *     SOLARIZE_ADD      i < 128 ? min(255, i + iarg) : i, iarg = 0..255                (timm's solarize_add)
+ *     AUTOCONTRAST      per channel, lo / hi = the histogram's lowest / highest non-empty bin: identity if hi <= lo, else in double
+ *                       scale = 255.0 / (hi - lo), offset = -lo * scale, lut[i] = clip((int)(i * scale + offset), 0, 255)
+ *                                                                                      (ImageOps.autocontrast, cutoff 0)
+ *     EQUALIZE          per channel, step = (pixels - count of the last non-empty bin) / 255 (integers): identity if at most one
+ *                       bin is non-empty or step == 0, else n = step / 2; lut[i] = min(255, n / step); n += h[i]
+ *                                                                                      (ImageOps.equalize)
+ *   blends              Image.blend(degenerate, image, factor) (ImageEnhance.*.enhance) in float32, one rounding per operator:
+ *                       t = (float)d + alpha * (float)(x - d), alpha = factor; the byte is (uint8)t when 0 <= alpha <= 1, else 0 if
+ *                       t <= 0, 255 if t >= 255, else (uint8)t (truncation).  The degenerate d:
+ *     BRIGHTNESS        0
+ *     COLOR             L = (R * 19595 + G * 38470 + B * 7471 + 0x8000) >> 16 in all three channels
+ *     CONTRAST          the constant (int)(mean(L) + 0.5), the mean = the integer sum of L over the image / pixels, in double
+ *     SHARPNESS         ImageFilter.SMOOTH per channel: (sum of the 3x3 neighbourhood + 4 * centre) / 13 + 0.5 truncated; the
+ *                       image's one-pixel border is the source's (there d = x).  PIL sums in float32; an integer sum s leaves
+ *                       s / 13 + 0.5 at least 1 / 26 from every integer, so the kernel's exact (2 s + 13) / 26 is the same byte.
+ *   AFFINE              Image.transform(size, AFFINE, m, resample = filter, fillcolor = fill), filter 2 (bilinear) or 3 (bicubic)
+ *                       PER RECORD, in double, one rounding per operator, left to right: for output pixel (x, y)
+ *                       xin = m0 (x + 0.5) + m1 (y + 0.5) + m2, yin likewise from m3..m5; fill where xin < 0, xin >= W, yin < 0 or
+ *                       yin >= H; else xin -= 0.5, yin -= 0.5, x0 = floor(xin), dx = xin - x0 (same in y), tap indices clamped
+ *                       to the image.  Bilinear: v = a + (b - a) d along x on rows y0, y0 + 1, then along y; (uint8)v.  Bicubic
+ *                       over taps x0 - 1 .. x0 + 2: p1 = v2, p2 = -v1 + v3, p3 = 2 (v1 - v2) + v3 - v4, p4 = -v1 + v2 - v3 + v4,
+ *                       v = p1 + d (p2 + d (p3 + d p4)) along x on four rows, then along y; 0 if v <= 0, 255 if v >= 255, else
+ *                       (uint8)v.  Rotations, shears and translations differ only in m (vitres/rand_augment.py builds them as
+ *                       PIL does).
+ * `ops` is a DEVICE array read at run time: a captured launch follows a table rewritten in place, and the entry point does no
+ * per-batch host work and no sync.  A record with an unknown op or filter, or iarg out of the ranges above, applies nothing;
+ * nothing outside the buffers is addressed whatever the table holds (vitres.kernels.rand_augment_u8 rejects such records on its
+ * host copy).  One launch, one workgroup per sample: it walks the sample's applied layers, the last one writing `out` and the ones
+ * before alternating between the sample's workspace plane and `out`, a workgroup barrier and a device fence between layers; the
+ * histograms and sums live in LDS.  workspace: vr_rand_augment_ws_bytes = B * 3 * H * W when layers > 1, else 0 (NULL allowed);
+ * never shared by launches that may run concurrently.  fill_rgb = r | g << 8 | b << 16.
+ * VR_EINVAL: a null pointer, src == out, a non-positive size, layers outside 1..4, a workspace that is missing, too small or one of
+ * src / out; VR_EUNSUPPORTED: W % 4, B > 65535, 3 * H * W >= 2^31; VR_EALIGN: src, out or workspace not 4-byte, ops not 8-byte
+ * aligned.  Checked before anything is launched.
+ */
+enum {
+    VR_RA_IDENTITY = 0, VR_RA_INVERT = 1, VR_RA_POSTERIZE = 2, VR_RA_SOLARIZE = 3, VR_RA_SOLARIZE_ADD = 4, VR_RA_AUTOCONTRAST = 5,
+    VR_RA_EQUALIZE = 6, VR_RA_BRIGHTNESS = 7, VR_RA_COLOR = 8, VR_RA_CONTRAST = 9, VR_RA_SHARPNESS = 10, VR_RA_AFFINE = 11
+};
+typedef struct vr_ra_op {
+    int32_t op;                /* VR_RA_*                                                                              */
+    int32_t filter;            /* AFFINE: 2 bilinear, 3 bicubic (PIL's numbers)                                        */
+    int32_t iarg;              /* POSTERIZE bits, SOLARIZE threshold, SOLARIZE_ADD addend                              */
+    float factor;              /* the blend ops' enhancement factor                                                    */
+    double m[6];               /* AFFINE: output -> source, as PIL's transform takes it                                */
+} vr_ra_op;                    /* 64 bytes */
+int vr_rand_augment_u8(const uint8_t* src /* [B,3,H,W] */, const vr_ra_op* ops /* device, [B, layers] */,
+                       uint8_t* out /* [B,3,H,W] */, int32_t B, int32_t H, int32_t W, int32_t layers,
+                       uint32_t fill_rgb, void* workspace, size_t ws_bytes, vr_stream_t stream);
+size_t vr_rand_augment_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t layers);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

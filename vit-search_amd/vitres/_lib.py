@@ -75,6 +75,14 @@ class ResampleBox(ctypes.Structure):
 VR_BILINEAR, VR_BICUBIC = 2, 3            # PIL's filter numbers
 
 
+class RaOp(ctypes.Structure):
+    _fields_ = [("op", c_int32), ("filter", c_int32), ("iarg", c_int32), ("factor", c_float), ("m", ctypes.c_double * 6)]
+
+
+(VR_RA_IDENTITY, VR_RA_INVERT, VR_RA_POSTERIZE, VR_RA_SOLARIZE, VR_RA_SOLARIZE_ADD, VR_RA_AUTOCONTRAST, VR_RA_EQUALIZE,
+ VR_RA_BRIGHTNESS, VR_RA_COLOR, VR_RA_CONTRAST, VR_RA_SHARPNESS, VR_RA_AFFINE) = range(12)
+
+
 # name -> argtypes ; every entry point returns int.  Must list every symbol of include/vitres_hip.h
 SYMBOLS = {
     "vr_version": [],
@@ -125,6 +133,7 @@ SYMBOLS = {
     "vr_mixup_u8_erase": [c_void_p] * 5 + [c_int32] * 5 + [c_float, c_float, c_void_p, c_void_p, ctypes.POINTER(EraseArgs), c_void_p],
     "vr_resample_u8": [c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, ctypes.c_size_t, c_void_p],
     "vr_resample_band_rows": [c_int32] * 6,
+    "vr_rand_augment_u8": [c_void_p, c_void_p, c_void_p] + [c_int32] * 4 + [ctypes.c_uint32, c_void_p, ctypes.c_size_t, c_void_p],
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],
@@ -155,6 +164,7 @@ SYMBOLS = {
 # the entry points that do not return int: name -> (argtypes, restype)
 OTHER_SYMBOLS = {
     "vr_resample_ws_bytes": ([c_int32, c_int32, c_int32], ctypes.c_size_t),
+    "vr_rand_augment_ws_bytes": ([c_int32] * 4, ctypes.c_size_t),
 }
 
 _lib = None

@@ -10,10 +10,11 @@ training, the `vr_token_mix_u8` pass of `SwitchTokenMix(input_norm=...)` -- make
   pad_collate_u8         a collate function for decoded images of different sizes: one zero-padded uint8 canvas per batch.
   DeviceCropLoader       canvases in, cropped / resized / mirrored uint8 [B,3,S,S] device batches out (vr_resample_u8 with the boxes
                          of a vitres.resized_crop transform): what the two classes above, SwitchTokenMix(input_norm=) and
-                         Mixup(input_norm=) take.
+                         Mixup(input_norm=) take.  augment=RandAugment(...) (vitres.rand_augment) runs the recipes' --aa stage on
+                         the cropped batch as well (vr_rand_augment_u8), so the default recipe's whole pixel chain is on the device.
 
-What is not here: decoding and the colour augmentations (RandAugment, ColorJitter -- they work on the cropped image, so a recipe that
-uses them still crops on the host) stay with the loader that produces the uint8 batches.  Random
+What is not here: decoding stays with the loader that produces the uint8 canvases.  ColorJitter is not implemented: timm skips it
+whenever auto_augment is set, so no shipped recipe runs it.  Random
 erasing, which timm applies to the normalised image, cannot happen there any more: `erase=` (a vitres.random_erasing.RandomErasing)
 folds it into the normalising pass -- here with normalize=True, in the mix (`SwitchTokenMix(..., erase=)`, `Mixup(..., erase=)`) in training.
 """
@@ -138,10 +139,16 @@ class DeviceCropLoader:
     the box table and the labels are copied one batch ahead on a side stream (the DevicePrefetchLoader pattern; pinned host batches
     make the copies asynchronous); the boxes are drawn, and checked against the canvas, in the loader's order when a batch is
     uploaded.  The output is what DevicePrefetchLoader, SwitchTokenMix(input_norm=), Mixup(input_norm=) and ResidentU8Batches take;
-    nothing is normalised here.  __len__, .sampler and .dataset are the wrapped loader's."""
+    nothing is normalised here.  augment=RandAugment(...) (vitres.rand_augment: .draw(B), .fill, .size): the batch's op table is drawn
+    after its boxes, copied with them, and vr_rand_augment_u8 runs on the cropped batch (3 channels); augment=None adds nothing.
+    __len__, .sampler and .dataset are the wrapped loader's."""
 
-    def __init__(self, loader, transform, device):
-        self.loader, self.transform, self.device = loader, transform, torch.device(device)
+    def __init__(self, loader, transform, device, augment=None):
+        self.loader, self.transform, self.device, self.augment = loader, transform, torch.device(device), augment
+        if augment is not None:
+            size = (transform.size, transform.size) if isinstance(transform.size, int) else tuple(transform.size)
+            if tuple(augment.size) != size:
+                raise ValueError("DeviceCropLoader: the augmentation draws for %s images, the transform makes %s" % (augment.size, size))
 
     def __len__(self):
         return len(self.loader)
@@ -165,11 +172,18 @@ class DeviceCropLoader:
         table = K.check_resample_boxes(self.transform.draw(sizes), B, Hs, Ws, self.transform.size)
         host = torch.empty(table.shape, dtype=torch.int32, pin_memory=side is not None)
         host.numpy()[...] = table
+        ops = None
+        if self.augment is not None:
+            ra = K.check_ra_table(self.augment.draw(B), B)
+            ops = torch.empty(ra.shape, dtype=torch.int32, pin_memory=side is not None)
+            ops.numpy()[...] = ra
         if side is None:                      # (not a GPU: nothing to overlap; the kernel itself has no CPU form)
-            return canvas.to(self.device), host.to(self.device), labels.to(self.device), None
+            return (canvas.to(self.device), host.to(self.device), labels.to(self.device), None,
+                    None if ops is None else ops.to(self.device))
         with torch.cuda.stream(side):
-            return (canvas.to(self.device, non_blocking=True), host.to(self.device, non_blocking=True),
-                    labels.to(self.device, non_blocking=True), side.record_event())
+            canvas, host, labels = (t.to(self.device, non_blocking=True) for t in (canvas, host, labels))
+            ops = None if ops is None else ops.to(self.device, non_blocking=True)
+            return canvas, host, labels, side.record_event(), ops
 
     def __iter__(self):
         side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
@@ -182,10 +196,13 @@ class DeviceCropLoader:
         if ahead is not None:
             yield self._hand_over(*ahead)
 
-    def _hand_over(self, canvas, table, labels, copied):
+    def _hand_over(self, canvas, table, labels, copied, ops=None):
         if copied is not None:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(copied)
-            for t in (canvas, table, labels):  # (allocated on the side stream, used on this one)
+            for t in (canvas, table, labels) + (() if ops is None else (ops,)):  # (allocated on the side stream, used on this one)
                 t.record_stream(cur)
-        return K.resample_u8(canvas, table, self.transform.size, self.transform.filter), labels
+        crop = K.resample_u8(canvas, table, self.transform.size, self.transform.filter)
+        if ops is None:
+            return crop, labels
+        return K.rand_augment_u8(crop, ops, self.augment.fill), labels

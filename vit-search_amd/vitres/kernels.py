@@ -1208,3 +1208,90 @@ def resample_u8(src, boxes, out_size, filter, out=None):
     _lib.check(_lib.lib().vr_resample_u8(_p(src), _p(table), _p(out), B, C, Hs, Ws, So_h, So_w, code, None, 0, _stream()),
                "vr_resample_u8")
     return out
+
+
+# ---- RandAugment on uint8 batches (vr_rand_augment_u8; vitres/rand_augment.py draws the tables) -------------------------------------------
+# op kinds of a record (VR_RA_* of include/vitres_hip.h): eleven kinds cover timm's fifteen ops, 'identity' is a drawn op not applied
+RA_OPS = {"identity": _lib.VR_RA_IDENTITY, "invert": _lib.VR_RA_INVERT, "posterize": _lib.VR_RA_POSTERIZE,
+          "solarize": _lib.VR_RA_SOLARIZE, "solarize_add": _lib.VR_RA_SOLARIZE_ADD, "autocontrast": _lib.VR_RA_AUTOCONTRAST,
+          "equalize": _lib.VR_RA_EQUALIZE, "brightness": _lib.VR_RA_BRIGHTNESS, "color": _lib.VR_RA_COLOR,
+          "contrast": _lib.VR_RA_CONTRAST, "sharpness": _lib.VR_RA_SHARPNESS, "affine": _lib.VR_RA_AFFINE}
+# one record of the device table (vr_ra_op, 64 bytes = 16 int32)
+RA_DTYPE = np.dtype([("op", "<i4"), ("filter", "<i4"), ("iarg", "<i4"), ("factor", "<f4"), ("m", "<f8", (6,))])
+RA_OP_INTS = ctypes.sizeof(_lib.RaOp) // 4
+assert RA_DTYPE.itemsize == ctypes.sizeof(_lib.RaOp) == 64 and RA_OP_INTS == 16
+RA_MAX_LAYERS = 4
+_RA_IARG = {_lib.VR_RA_POSTERIZE: (0, 8), _lib.VR_RA_SOLARIZE: (0, 256), _lib.VR_RA_SOLARIZE_ADD: (0, 255)}
+_RA_BLENDS = (_lib.VR_RA_BRIGHTNESS, _lib.VR_RA_COLOR, _lib.VR_RA_CONTRAST, _lib.VR_RA_SHARPNESS)
+
+
+def ra_table(B, layers):
+    """A host table of B x layers records (RA_DTYPE: op, filter, iarg, factor, m[6]), every record 'identity'."""
+    return np.zeros((B, layers), dtype=RA_DTYPE)
+
+
+def ra_fill(fill):
+    """(r, g, b) bytes -> the packed fill word r | g << 8 | b << 16"""
+    given, fill = tuple(fill), tuple(int(v) for v in fill)
+    if len(fill) != 3 or any(v < 0 or v > 255 or v != g for v, g in zip(fill, given)):
+        raise ValueError("rand_augment_u8: fill must be three bytes (r, g, b), got %r" % (given,))
+    return fill[0] | fill[1] << 8 | fill[2] << 16
+
+
+def check_ra_table(table, B, layers=None, what="vr_rand_augment_u8"):
+    """table (RA_DTYPE [B, layers]) as the contiguous int32 [B, layers, 16] array the device reads, with every record checked: a known
+    op; filter 2 / 3 and a finite matrix for 'affine'; posterize bits 0..8, solarize threshold 0..256, solarize_add addend 0..255;
+    a finite factor for the blends.  The device treats a bad record as identity and cannot report it, so the host copy is what is
+    checked: RuntimeError VR_EINVAL, before anything is launched."""
+    table = np.asarray(table)
+    if table.dtype != RA_DTYPE or table.ndim != 2 or table.shape[0] != B or (layers is not None and table.shape[1] != layers) \
+            or not 1 <= table.shape[1] <= RA_MAX_LAYERS:
+        raise ValueError("%s: the op table must be a %s array of shape (%d, %s), 1..%d layers; got %s %s" % (
+            what, "ra_table", B, "layers" if layers is None else layers, RA_MAX_LAYERS, table.dtype, table.shape))
+    table = np.ascontiguousarray(table)
+    op, filt, iarg = table["op"], table["filter"], table["iarg"]
+    bad = (op < 0) | (op > _lib.VR_RA_AFFINE)
+    bad |= (op == _lib.VR_RA_AFFINE) & (((filt != _lib.VR_BILINEAR) & (filt != _lib.VR_BICUBIC)) | ~np.isfinite(table["m"]).all(axis=-1))
+    for code, (lo, hi) in _RA_IARG.items():
+        bad |= (op == code) & ((iarg < lo) | (iarg > hi))
+    bad |= np.isin(op, _RA_BLENDS) & ~np.isfinite(table["factor"])
+    if bad.any():
+        b, k = (int(v[0]) for v in np.nonzero(bad))
+        r = table[b, k]
+        raise RuntimeError("%s failed: %s: sample %d, layer %d: op=%d filter=%d iarg=%d factor=%r m=%s is not a record the kernel "
+                           "applies" % (what, _lib._ERR[-1], b, k, r["op"], r["filter"], r["iarg"], float(r["factor"]), r["m"].tolist()))
+    return table.view(np.int32).reshape(B, table.shape[1], RA_OP_INTS)
+
+
+def rand_augment_u8(src, table, fill, out=None):
+    """vr_rand_augment_u8: every sample's records applied in order to the uint8 [B,3,H,W] batch src (W % 4 == 0), bit for bit what PIL
+    makes of the RGB image with timm's RandAugment ops (the header states each op).  table: a host RA_DTYPE array [B, layers]
+    (ra_table; vitres.rand_augment.RandAugment.draw) -- checked, then uploaded from pinned memory on the current stream without a
+    host wait -- or an int32 [B, layers, 16] DEVICE tensor the caller has checked (check_ra_table) and may rewrite in place between
+    replays of a captured launch.  fill: the (r, g, b) bytes the affine ops put where they map outside the image; out: a
+    preallocated result (not src).  With more than one layer a workspace of the batch's size is taken from torch's allocator."""
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[1] != 3:
+        raise TypeError("rand_augment_u8: a uint8 [B,3,H,W] tensor expected, got %s %s" % (src.dtype, tuple(src.shape)))
+    B, _, H, W = src.shape
+    word = ra_fill(fill)
+    _p(src)
+    if isinstance(table, torch.Tensor):
+        if table.dtype != torch.int32 or table.dim() != 3 or table.shape[0] != B or table.shape[2] != RA_OP_INTS \
+                or not table.is_contiguous() or table.device != src.device:
+            raise ValueError("rand_augment_u8: a device op table must be a contiguous int32 [%d, layers, %d] tensor on %s" % (
+                B, RA_OP_INTS, src.device))
+        dev_table = table
+    else:
+        dev_table = _upload_i32(check_ra_table(table, B), src.device)
+    layers = int(dev_table.shape[1])
+    src = src.contiguous()
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(src.shape) or not out.is_contiguous() or out.device != src.device:
+        raise ValueError("rand_augment_u8: out must be a contiguous uint8 tensor of shape %s on %s" % (tuple(src.shape), src.device))
+    L = _lib.lib()
+    need = int(L.vr_rand_augment_ws_bytes(B, H, W, layers)) if 1 <= layers <= RA_MAX_LAYERS else 0
+    ws = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
+    _lib.check(L.vr_rand_augment_u8(_p(src), _p(dev_table), _p(out), B, H, W, layers, word, _p(ws), need, _stream()),
+               "vr_rand_augment_u8")
+    return out

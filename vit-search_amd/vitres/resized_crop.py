@@ -9,9 +9,10 @@ timm and torchvision are not vendored by the reference and are not importable he
 theirs, and parity is NOT pinned at that boundary by a golden file.  What IS pinned is the pixel side: vr_resample_u8 against PIL
 itself (tests/golden/f20_resample_pil.npz).
 
-What is not here: RandAugment and ColorJitter sit between the flip and ToTensor and work on the cropped image; they stay on the
-host, so a recipe that uses them (--aa, --color-jitter) cannot take the device crop yet.  interpolation='random' (timm picks
-bilinear or bicubic per sample) is not implemented: one launch has one filter.
+What is not here: RandAugment, which sits between the flip and ToTensor, is vitres/rand_augment.py and runs on this stage's output
+(DeviceCropLoader(augment=)).  ColorJitter is not implemented: timm skips it whenever auto_augment is set, so no shipped recipe runs
+it.  Decoding stays on the host.  interpolation='random' (timm picks bilinear or bicubic per sample) is not implemented: one launch
+has one filter.
 """
 import math
 import random
