@@ -267,6 +267,7 @@ int vr_cast_transpose_batch(const float* src, void* dst, const vr_tr_desc* descs
  * parameters start at multiples of 8) selects groups[...]; 255 = elements that are not updated (padding, frozen).
  *   p *= 1 - lr*wd ; m = b1 m + (1-b1) g ; v = b2 v + (1-b2) g^2 ; p -= lr/bias_c1 * m / (sqrt(v)/sqrt_bias_c2 + eps)
  * with bias_c1 = 1 - b1^t, sqrt_bias_c2 = sqrt(1 - b2^t) computed by the caller for step t.  n % 8 == 0.
+ * The EMA's 1-d is taken on the fp32 d (weights sum to exactly 1); ModelEmaV2 rounds the double 1-d: 1.3e-4 apart at d = 0.99996.
  */
 #define VR_ADAMW_MAX_GROUPS 16
 typedef struct vr_adamw_group {

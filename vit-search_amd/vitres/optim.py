@@ -251,12 +251,17 @@ class FlatAdamW(torch.optim.Optimizer):
         return loss
 
     # ---- the update as part of a captured hipGraph ---------------------------------------------------------------------
+    @staticmethod
+    def _bias_corrections(b1, b2, t):
+        """(bias_c1, sqrt_bias_c2) of step t in double, before vr_adamw_group rounds them to fp32"""
+        return 1.0 - b1 ** t, math.sqrt(1.0 - b2 ** t)
+
     def _group_structs(self, t):
         arr = (_Group * len(self.param_groups))()
         for gi, group in enumerate(self.param_groups):
             b1, b2 = group["betas"]
-            arr[gi] = _Group(group["lr"], b1, b2, group["eps"], group["weight_decay"], 1.0 - b1 ** t,
-                             math.sqrt(1.0 - b2 ** t), self._grad_factor())
+            bias_c1, sqrt_bias_c2 = self._bias_corrections(b1, b2, t)
+            arr[gi] = _Group(group["lr"], b1, b2, group["eps"], group["weight_decay"], bias_c1, sqrt_bias_c2, self._grad_factor())
         return arr
 
     def prepare_step(self, apply=True):
