@@ -675,6 +675,59 @@ int vr_rand_augment_u8(const uint8_t* src /* [B,3,H,W] */, const vr_ra_op* ops /
 size_t vr_rand_augment_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t layers);
 
 /*
+ * The device half of JPEG decoding.  The host half (libvitres_jpeg.so, include/vitres_jpeg.h) Huffman-decodes every baseline stream
+ * of a batch into quantised coefficients; this entry makes of them exactly the canvas batch pad_collate_u8 would have made of
+ * PIL's Image.open(f).convert('RGB') of the same files (PIL 12 with libjpeg-turbo): every image top-left in its [3,Hs,Ws] planes,
+ * every other byte zero, grayscale streams in all three planes.  The launch writes EVERY byte of the canvas; the caller does not
+ * clear it.
+ *   blob    the batch's data, `blob_bytes` of it.  kind VR_JPEG_COEF: per component, the blocks of its block-padded plane (bh rows of
+ *           bw blocks) in raster order, 64 int16 per block in natural (row-major) order, as vr_jpeg_entropy_decode writes them.
+ *           kind VR_JPEG_RAW (files the host decoded some other way): three planes R, G, B of uint8, each bh * 8 rows of bw * 8 bytes.
+ *   descs   one record per image (below); off[c] is the component's offset into the blob in units of 16 bytes.
+ *   qtabs   uint16 [B,3,64]: the quantisation table of each component in natural order (unused by raw records).
+ *   workspace  vr_jpeg_ws_bytes(blob_bytes) = blob_bytes / 2 rounded up to 16: the component sample planes between the two launches
+ *           (a sample is one byte where a coefficient was two, so component c of a record lives at off[c] * 8); never shared by
+ *           launches that may run concurrently.
+ * Arithmetic, all in 32-bit integers that wrap (unsigned operations, arithmetic right shifts), clamped to 0..255 at the end:
+ *   dequantise   coefficient * table entry
+ *   inverse DCT  libjpeg's jidctint (ISLOW), CONST_BITS 13, PASS1_BITS 2: columns first, descaled by 11 bits, then rows, descaled by
+ *                18 bits, each descale adding half and shifting arithmetically; constants 2446 3196 4433 6270 7373 9633 12299
+ *                15137 16069 16819 20995 25172; then + 128 and the clamp
+ *   chroma       plane size dw = ceil(W / hs), dh = ceil(H / vs); edges replicate within that size, not the block padding.
+ *                2x1, dw > 2: out[2i] = (3 p[i] + p[i-1] + 1) >> 2, out[2i+1] = (3 p[i] + p[i+1] + 2) >> 2.
+ *                2x2, dw > 2: t = 3 p[r] + p[r-1] for the upper output row of input row r, 3 p[r] + p[r+1] for the lower; then
+ *                out[2i] = (3 t[i] + t[i-1] + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4.  dw <= 2: every sample repeated.
+ *   colour       with cb, cr minus 128: R = Y + ((91881 cr + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *                B = Y + ((116130 cb + 32768) >> 16)
+ * For coefficients no encoder emits (products beyond 16 bits) the pixels are unspecified, the accesses are not.
+ * `descs` and `qtabs` are DEVICE arrays read at run time; the entry does no per-batch host work and no sync.  The device checks
+ * every record before it reads anything through it: kind 0 / 1; 1 <= width <= min(Ws, 8192), 1 <= height <= min(Hs, 8192); ncomp 1
+ * with hs = vs = 1, or ncomp 3 with (hs, vs) one of (1,1) (2,1) (2,2) -- raw: ncomp 3, hs = vs = 1; bw[0] = hs * ceil(width / (8 hs)),
+ * bh[0] = vs * ceil(height / (8 vs)), bw[c] = bw[0] / hs and bh[c] = bh[0] / vs for the chroma; off[c] >= 0 and the component's bytes
+ * (128 per block, 64 for raw) inside blob_bytes.  A record that fails leaves its image's planes zero and nothing is read for it;
+ * no record, valid or not, makes the launches address anything outside the buffers (vitres.kernels.check_jpeg_table rejects such
+ * records on the host copy).
+ * VR_EINVAL: a null pointer, a non-positive size, a workspace that is missing, too small, or one of blob / canvas; VR_EUNSUPPORTED:
+ * Ws % 4, B > 65535, Hs or Ws above 8192 (the sides a record may have: a baseline frame allows 65535, 8192 keeps every index of a
+ * plane inside 32 bits with room to spare); VR_EALIGN: blob or workspace not 16-byte, canvas or descs not 4-byte, qtabs not 2-byte
+ * aligned.  Checked before anything is launched.
+ */
+enum { VR_JPEG_COEF = 0, VR_JPEG_RAW = 1 };
+typedef struct vr_jpeg_desc {
+    int32_t kind;              /* VR_JPEG_COEF / VR_JPEG_RAW                                                           */
+    int32_t width, height;
+    int32_t ncomp;             /* 1 (grayscale) or 3                                                                   */
+    int32_t hs, vs;            /* luma sampling factors (chroma is 1 x 1)                                              */
+    int32_t off[3];            /* offset of component c in the blob, units of 16 bytes                                 */
+    int32_t bw[3], bh[3];      /* the component's plane in 8 x 8 blocks, padded to whole MCUs                          */
+    int32_t reserved;
+} vr_jpeg_desc;                /* 64 bytes */
+int vr_jpeg_reconstruct_u8(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs /* device, [B] */,
+                           const uint16_t* qtabs /* device, [B,3,64] */, uint8_t* canvas /* [B,3,Hs,Ws] */, int32_t B, int32_t Hs,
+                           int32_t Ws, void* workspace, size_t ws_bytes, vr_stream_t stream);
+size_t vr_jpeg_ws_bytes(int64_t blob_bytes);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

@@ -1,4 +1,5 @@
-"""ctypes loader for libvitres_hip.so (the C ABI declared in include/vitres_hip.h).
+"""ctypes loaders for libvitres_hip.so (the C ABI declared in include/vitres_hip.h) and for libvitres_jpeg.so (the host-only JPEG
+entropy decoder of include/vitres_jpeg.h: `jpeg_lib()`, which never touches the HIP library -- DataLoader workers load only that).
 
 The library is the product: there is no CPU / PyTorch fallback.  Importing this module never fails
 (so that host-side logic can be unit-tested without a GPU), but the first kernel call raises
@@ -11,6 +12,8 @@ from ctypes import c_float, c_int32, c_int64, c_uint64, c_void_p
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VITRES_LIB: another build of the same ABI (A/B timing of kernel changes on one box: tools/ab.sh)
 LIB_PATH = os.environ.get("VITRES_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvitres_hip.so")
+
+JPEG_LIB_PATH = os.environ.get("VITRES_JPEG_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvitres_jpeg.so")
 
 VR_F32, VR_BF16, VR_F16 = 0, 1, 2
 
@@ -83,6 +86,19 @@ class RaOp(ctypes.Structure):
  VR_RA_BRIGHTNESS, VR_RA_COLOR, VR_RA_CONTRAST, VR_RA_SHARPNESS, VR_RA_AFFINE) = range(12)
 
 
+class JpegDesc(ctypes.Structure):
+    _fields_ = [("kind", c_int32), ("width", c_int32), ("height", c_int32), ("ncomp", c_int32), ("hs", c_int32), ("vs", c_int32),
+                ("off", c_int32 * 3), ("bw", c_int32 * 3), ("bh", c_int32 * 3), ("reserved", c_int32)]
+
+
+VR_JPEG_COEF, VR_JPEG_RAW = 0, 1
+
+
+class JpegInfo(ctypes.Structure):                 # include/vitres_jpeg.h
+    _fields_ = [("supported", c_int32), ("width", c_int32), ("height", c_int32), ("ncomp", c_int32), ("hs", c_int32), ("vs", c_int32),
+                ("restart_interval", c_int32), ("blocks", c_int32 * 3), ("bw", c_int32 * 3), ("bh", c_int32 * 3)]
+
+
 # name -> argtypes ; every entry point returns int.  Must list every symbol of include/vitres_hip.h
 SYMBOLS = {
     "vr_version": [],
@@ -134,6 +150,8 @@ SYMBOLS = {
     "vr_resample_u8": [c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, ctypes.c_size_t, c_void_p],
     "vr_resample_band_rows": [c_int32] * 6,
     "vr_rand_augment_u8": [c_void_p, c_void_p, c_void_p] + [c_int32] * 4 + [ctypes.c_uint32, c_void_p, ctypes.c_size_t, c_void_p],
+    "vr_jpeg_reconstruct_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, ctypes.c_size_t,
+                               c_void_p],
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],
@@ -165,6 +183,13 @@ SYMBOLS = {
 OTHER_SYMBOLS = {
     "vr_resample_ws_bytes": ([c_int32, c_int32, c_int32], ctypes.c_size_t),
     "vr_rand_augment_ws_bytes": ([c_int32] * 4, ctypes.c_size_t),
+    "vr_jpeg_ws_bytes": ([c_int64], ctypes.c_size_t),
+}
+
+# the host-only library: name -> argtypes, every entry returns int
+JPEG_SYMBOLS = {
+    "vr_jpeg_probe": [c_void_p, c_int64, ctypes.POINTER(JpegInfo)],
+    "vr_jpeg_entropy_decode": [c_void_p, c_int64, ctypes.POINTER(JpegInfo), c_void_p, c_int64, c_void_p],
 }
 
 _lib = None
@@ -178,6 +203,9 @@ def lib():
             raise RuntimeError(
                 "libvitres_hip.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C vit-search_amd/csrc`).  There is no CPU fallback." % LIB_PATH)
+        # torch first: it ships its own HIP runtime, and the library must bind to that copy -- loaded ahead of torch it would bring
+        # in the system's, and two runtimes in one process do not share devices, streams or memory
+        import torch  # noqa: F401
         L = ctypes.CDLL(LIB_PATH)
         for name, argtypes in SYMBOLS.items():
             try:
@@ -194,6 +222,29 @@ def lib():
             fn.argtypes, fn.restype = argtypes, restype
         _lib = L
     return _lib
+
+
+_jpeg_lib = None
+
+
+def jpeg_lib():
+    """Load (once) and return libvitres_jpeg.so.  Plain host code: loading it pulls in neither libvitres_hip.so nor the HIP runtime."""
+    global _jpeg_lib
+    if _jpeg_lib is None:
+        if not os.path.exists(JPEG_LIB_PATH):
+            raise RuntimeError(
+                "libvitres_jpeg.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(or `make -C vit-search_amd/csrc`)." % JPEG_LIB_PATH)
+        L = ctypes.CDLL(JPEG_LIB_PATH)
+        for name, argtypes in JPEG_SYMBOLS.items():
+            try:
+                fn = getattr(L, name)
+            except AttributeError as e:
+                raise RuntimeError("libvitres_jpeg.so does not export %s" % name) from e
+            fn.argtypes = argtypes
+            fn.restype = ctypes.c_int
+        _jpeg_lib = L
+    return _jpeg_lib
 
 
 _ERR = {-1: "VR_EINVAL (bad argument)", -2: "VR_EALIGN (pointer / leading-dimension alignment)",

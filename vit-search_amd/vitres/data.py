@@ -13,14 +13,23 @@ training, the `vr_token_mix_u8` pass of `SwitchTokenMix(input_norm=...)` -- make
                          Mixup(input_norm=) take.  augment=RandAugment(...) (vitres.rand_augment) runs the recipes' --aa stage on
                          the cropped batch as well (vr_rand_augment_u8), so the default recipe's whole pixel chain is on the device.
 
-What is not here: decoding stays with the loader that produces the uint8 canvases.  ColorJitter is not implemented: timm skips it
+  jpeg_collate           a collate function for ENCODED files: baseline JPEG streams are Huffman-decoded on the host
+                         (libvitres_jpeg.so, vitres.jpeg) into one coefficient blob per batch; anything else is decoded by PIL.
+  DeviceJpegLoader       those blobs in, the canvases pad_collate_u8 would have made out -- on the device (vr_jpeg_reconstruct_u8:
+                         dequantise, inverse DCT, chroma upsampling, colour conversion, placement): what DeviceCropLoader takes.
+
+What is not here: the entropy decoding of JPEG stays on host cores (in the loader's workers); progressive, arithmetic-coded and
+non-JPEG files are decoded there entirely, by PIL.  ColorJitter is not implemented: timm skips it
 whenever auto_augment is set, so no shipped recipe runs it.  Random
 erasing, which timm applies to the normalised image, cannot happen there any more: `erase=` (a vitres.random_erasing.RandomErasing)
 folds it into the normalising pass -- here with normalize=True, in the mix (`SwitchTokenMix(..., erase=)`, `Mixup(..., erase=)`) in training.
 """
+import io
+
 import numpy as np
 import torch
 
+from . import jpeg as J
 from . import kernels as K
 
 
@@ -206,3 +215,133 @@ class DeviceCropLoader:
         if ops is None:
             return crop, labels
         return K.rand_augment_u8(crop, ops, self.augment.fill), labels
+
+
+def _pil_rgb(data):
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+
+
+def jpeg_collate(samples):
+    """Collate a list of (encoded file bytes, label) into
+    (blob uint8 [n], descs int32 [B,16], qtabs int16 [B,3,64] (uint16 bits), sizes int32 [B,2] of (h, w), labels int64 [B]) --
+    plain tensors, so pin_memory=True works -- for DeviceJpegLoader / kernels.jpeg_reconstruct_u8.  A stream vitres.jpeg.probe calls
+    supported is Huffman-decoded straight into the blob (record kind 0: quantised coefficients, per component, 128 bytes a block).
+    Every other file, and every stream whose entropy decode fails, is decoded by PIL's Image.open(...).convert('RGB') and stored as
+    planar pixels (kind 1): the fallback is PIL's result by construction, PIL's exception for a file it cannot read included.  Every
+    image starts on a multiple of 128 bytes, every component on a multiple of its block size (128 bytes, 64 for pixels)."""
+    if not samples:
+        raise ValueError("jpeg_collate: an empty batch")
+    B = len(samples)
+    files = [data if isinstance(data, (bytes, np.ndarray)) else bytes(data) for data, _ in samples]
+    infos, raws, slots, total = [], [], [], 0
+    for data in files:
+        info = J.probe(data)
+        raw = None if info["supported"] else _pil_rgb(data)
+        H, W = (info["height"], info["width"]) if raw is None else raw.shape[:2]
+        size = 3 * 64 * (-(-H // 8)) * (-(-W // 8))                        # as raw pixels (what a failed entropy decode falls back to)
+        if raw is None:
+            size = max(size, 128 * sum(info["blocks"]))
+        size = -(-size // 128) * 128
+        infos.append(info)
+        raws.append(raw)
+        slots.append((total, size))
+        total += size
+    blob = np.zeros(total, dtype=np.uint8)
+    descs = K.jpeg_descs(B)
+    qtabs = np.zeros((B, 3, 64), dtype=np.uint16)
+    sizes = np.zeros((B, 2), dtype=np.int32)
+    for b, (data, info, raw, (lo, size)) in enumerate(zip(files, infos, raws, slots)):
+        d = descs[b]
+        if raw is None:
+            try:
+                J.entropy_decode(data, coef=blob[lo:lo + size].view(np.int16), qtab=qtabs[b])
+            except J.JpegError:
+                blob[lo:lo + size] = 0
+                qtabs[b] = 0
+                raw = _pil_rgb(data)
+        if raw is None:
+            d["kind"], d["width"], d["height"], d["ncomp"] = K._lib.VR_JPEG_COEF, info["width"], info["height"], info["ncomp"]
+            d["hs"], d["vs"] = info["hs"], info["vs"]
+            off = lo
+            for c in range(info["ncomp"]):
+                d["off"][c], d["bw"][c], d["bh"][c] = off // K.JPEG_OFF_UNIT, info["bw"][c], info["bh"][c]
+                off += 128 * info["blocks"][c]
+        else:
+            H, W = raw.shape[:2]
+            bh, bw = -(-H // 8), -(-W // 8)
+            d["kind"], d["width"], d["height"], d["ncomp"], d["hs"], d["vs"] = K._lib.VR_JPEG_RAW, W, H, 3, 1, 1
+            planes = blob[lo:lo + 3 * 64 * bh * bw].reshape(3, bh * 8, bw * 8)
+            planes[:, :H, :W] = raw.transpose(2, 0, 1)
+            for c in range(3):
+                d["off"][c], d["bw"][c], d["bh"][c] = (lo + c * 64 * bh * bw) // K.JPEG_OFF_UNIT, bw, bh
+        sizes[b] = d["height"], d["width"]
+    labels = torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
+    return (torch.from_numpy(blob), torch.from_numpy(descs.view(np.int32).reshape(B, K.JPEG_DESC_INTS)),
+            torch.from_numpy(qtabs.view(np.int16)), torch.from_numpy(sizes), labels)
+
+
+class DeviceJpegLoader:
+    """Over a loader of jpeg_collate batches (DataLoader(..., collate_fn=jpeg_collate, pin_memory=True)): yields
+    (canvas uint8 [B,3,Hs,Ws] on `device`, sizes [B,2] on the host, labels), the triple DeviceCropLoader takes from a pad_collate_u8
+    loader -- the same bytes, made on the device by vr_jpeg_reconstruct_u8 from the coefficients the workers decoded.  Hs, Ws are the
+    batch maxima rounded up to multiples of 4.  The blob, the record table and the quantisation tables are copied one batch ahead on
+    a side stream (the DevicePrefetchLoader pattern); the records are checked against the blob and the canvas on the host copy when
+    a batch is uploaded.  The canvases alternate between TWO buffers and the launches share one workspace, all kept and grown as
+    batches need: a yielded canvas is valid until the batch after next is requested, which is what a consumer that launches on the
+    current stream -- DeviceCropLoader -- needs.  __len__, .sampler and .dataset are the wrapped loader's."""
+
+    def __init__(self, loader, device):
+        self.loader, self.device = loader, torch.device(device)
+        self._canvas, self._ws, self._turn = [None, None], None, 0
+
+    def __len__(self):
+        return len(self.loader)
+
+    @property
+    def sampler(self):
+        return self.loader.sampler
+
+    @property
+    def dataset(self):
+        return self.loader.dataset
+
+    def _upload(self, side, blob, descs, qtabs, sizes, labels):
+        if blob.dtype != torch.uint8 or blob.dim() != 1 or descs.dtype != torch.int32 or descs.dim() != 2:
+            raise TypeError("DeviceJpegLoader takes jpeg_collate batches (blob uint8 [n], descs int32 [B,16], ...)")
+        Hs, Ws = ((int(v) + 3) // 4 * 4 for v in np.asarray(sizes).max(axis=0))
+        K.check_jpeg_table(descs.numpy(), int(blob.numel()), Hs, Ws)
+        if side is None:                      # (not a GPU: nothing to overlap; the kernel itself has no CPU form)
+            return blob.to(self.device), descs.to(self.device), qtabs.to(self.device), sizes, labels, Hs, Ws, None
+        with torch.cuda.stream(side):
+            blob, descs, qtabs = (t.to(self.device, non_blocking=True) for t in (blob, descs, qtabs))
+            return blob, descs, qtabs, sizes, labels, Hs, Ws, side.record_event()
+
+    def __iter__(self):
+        side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
+        ahead = None
+        for batch in self.loader:
+            nxt = self._upload(side, *batch)
+            if ahead is not None:
+                yield self._hand_over(*ahead)
+            ahead = nxt
+        if ahead is not None:
+            yield self._hand_over(*ahead)
+
+    def _buffer(self, held, nbytes):
+        if held is None or held.numel() < nbytes:
+            held = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return held
+
+    def _hand_over(self, blob, descs, qtabs, sizes, labels, Hs, Ws, copied):
+        if copied is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(copied)
+            for t in (blob, descs, qtabs):    # (allocated on the side stream, used on this one)
+                t.record_stream(cur)
+        B = int(descs.shape[0])
+        turn, self._turn = self._turn, self._turn ^ 1
+        self._canvas[turn] = self._buffer(self._canvas[turn], B * 3 * Hs * Ws)
+        self._ws = self._buffer(self._ws, K.jpeg_ws_bytes(blob.numel()))
+        canvas = self._canvas[turn][:B * 3 * Hs * Ws].view(B, 3, Hs, Ws)
+        return K.jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=canvas, workspace=self._ws), sizes, labels

@@ -1295,3 +1295,113 @@ def rand_augment_u8(src, table, fill, out=None):
     _lib.check(L.vr_rand_augment_u8(_p(src), _p(dev_table), _p(out), B, H, W, layers, word, _p(ws), need, _stream()),
                "vr_rand_augment_u8")
     return out
+
+
+# ---- JPEG: the device half of decoding (vr_jpeg_reconstruct_u8; vitres/jpeg.py is the host half, vitres/data.py the loader) ---------------
+# one record of the device table (vr_jpeg_desc, 64 bytes = 16 int32)
+JPEG_DESC_DTYPE = np.dtype([("kind", "<i4"), ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"),
+                            ("off", "<i4", (3,)), ("bw", "<i4", (3,)), ("bh", "<i4", (3,)), ("reserved", "<i4")])
+JPEG_DESC_INTS = ctypes.sizeof(_lib.JpegDesc) // 4
+assert JPEG_DESC_DTYPE.itemsize == ctypes.sizeof(_lib.JpegDesc) == 64 and JPEG_DESC_INTS == 16
+JPEG_MAX_SIDE = 8192
+JPEG_OFF_UNIT = 16                         # bytes per unit of vr_jpeg_desc.off
+
+
+def jpeg_descs(B):
+    """A zeroed host table of B records (JPEG_DESC_DTYPE: kind, width, height, ncomp, hs, vs, off[3], bw[3], bh[3])."""
+    return np.zeros(B, dtype=JPEG_DESC_DTYPE)
+
+
+def jpeg_ws_bytes(blob_bytes):
+    """vr_jpeg_ws_bytes: the workspace a launch over a blob of that size needs (the component sample planes: half the blob)."""
+    n = int(blob_bytes)
+    return ((n + 1) // 2 + 15) & ~15 if n > 0 else 0
+
+
+def check_jpeg_table(descs, blob_bytes, Hs, Ws, what="vr_jpeg_reconstruct_u8"):
+    """descs (JPEG_DESC_DTYPE [B], or int32 [B, 16]) as the contiguous int32 [B, 16] array the device reads, with every record
+    checked as the device checks it (the header lists the rules: kind, sides inside the canvas and 8192, sampling, block-plane sizes
+    that follow from the sides, offsets inside the blob) and, beyond that, no two components overlapping.  The device zeroes the
+    image of a bad record and cannot report it, so the host copy is what is checked: RuntimeError VR_EINVAL, before any launch."""
+    descs = np.asarray(descs)
+    if descs.dtype != JPEG_DESC_DTYPE:
+        if descs.dtype != np.int32 or descs.ndim != 2 or descs.shape[1] != JPEG_DESC_INTS:
+            raise ValueError("%s: the record table must be a jpeg_descs array or int32 [B, %d], got %s %s" % (
+                what, JPEG_DESC_INTS, descs.dtype, descs.shape))
+        descs = np.ascontiguousarray(descs).view(JPEG_DESC_DTYPE).reshape(-1)
+    if descs.ndim != 1 or descs.shape[0] < 1:
+        raise ValueError("%s: the record table must hold one record per image, got shape %s" % (what, descs.shape))
+    descs = np.ascontiguousarray(descs)
+    kind, W, H, nc, hs, vs = (descs[k].astype(np.int64) for k in ("kind", "width", "height", "ncomp", "hs", "vs"))
+    off, bw, bh = (descs[k].astype(np.int64) for k in ("off", "bw", "bh"))
+    raw = kind == _lib.VR_JPEG_RAW
+    bad = ((kind != _lib.VR_JPEG_COEF) & ~raw) | (W < 1) | (W > min(Ws, JPEG_MAX_SIDE)) | (H < 1) | (H > min(Hs, JPEG_MAX_SIDE))
+    samp = (hs == 1) & (vs == 1)
+    bad |= raw & ~((nc == 3) & samp)
+    bad |= ~raw & ~(((nc == 1) & samp) | ((nc == 3) & (samp | ((hs == 2) & ((vs == 1) | (vs == 2))))))
+    hs_, vs_ = np.clip(hs, 1, 2), np.clip(vs, 1, 2)
+    mx, my = -(-W // (8 * hs_)), -(-H // (8 * vs_))
+    unit = np.where(raw, 64, 128)
+    spans = []
+    for c in range(3):
+        live = c < nc
+        size = bw[:, c] * bh[:, c] * unit
+        bad |= live & ((bw[:, c] != mx * (hs_ if c == 0 else 1)) | (bh[:, c] != my * (vs_ if c == 0 else 1)) | (off[:, c] < 0)
+                       | (off[:, c] * JPEG_OFF_UNIT + size > blob_bytes))
+        spans += [(int(off[b, c]) * JPEG_OFF_UNIT, int(size[b]), b) for b in np.flatnonzero(live & ~bad)]
+    if not bad.any():
+        spans.sort()
+        for (lo, n, _), (lo2, _, b2) in zip(spans, spans[1:]):
+            if lo + n > lo2:
+                bad[b2] = True
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        r = descs[i]
+        raise RuntimeError("%s failed: %s: image %d: kind=%d %dx%d ncomp=%d sampling=%dx%d off=%s bw=%s bh=%s is not a record the "
+                           "kernel takes for a %d-byte blob and a %d x %d canvas (or it overlaps another)" % (
+                               what, _lib._ERR[-1], i, r["kind"], r["width"], r["height"], r["ncomp"], r["hs"], r["vs"],
+                               r["off"].tolist(), r["bw"].tolist(), r["bh"].tolist(), blob_bytes, Hs, Ws))
+    return descs.view(np.int32).reshape(descs.shape[0], JPEG_DESC_INTS)
+
+
+def jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=None, workspace=None):
+    """vr_jpeg_reconstruct_u8: the batch's coefficient blob (uint8 device tensor, 1-D, as vitres.data.jpeg_collate lays it out) ->
+    the uint8 canvas [B,3,Hs,Ws] pad_collate_u8 would have made of PIL's decoded images, bit for bit; every byte of it is written.
+    descs: a host table (jpeg_descs / int32 [B, 16]) -- checked (check_jpeg_table), then uploaded from pinned memory on the current
+    stream without a host wait -- or an int32 [B, 16] DEVICE tensor the caller has checked.  qtabs: the quantisation tables
+    [B,3,64], uint16 bits in an int16 / uint16 tensor on the device, or a host uint16 array.  out: a preallocated canvas; workspace:
+    a uint8 device tensor of at least jpeg_ws_bytes(blob.numel()) bytes (taken from torch's allocator when None)."""
+    if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
+        raise TypeError("jpeg_reconstruct_u8: the blob is a contiguous 1-D uint8 tensor, got %s %s" % (blob.dtype, tuple(blob.shape)))
+    _p(blob)
+    dev, nbytes, Hs, Ws = blob.device, int(blob.numel()), int(Hs), int(Ws)
+    if isinstance(descs, torch.Tensor):
+        if descs.dtype != torch.int32 or descs.dim() != 2 or descs.shape[1] != JPEG_DESC_INTS or not descs.is_contiguous() \
+                or descs.device != dev:
+            raise ValueError("jpeg_reconstruct_u8: a device record table must be a contiguous int32 [B, %d] tensor on %s" % (
+                JPEG_DESC_INTS, dev))
+        table = descs
+    else:
+        table = _upload_i32(check_jpeg_table(descs, nbytes, Hs, Ws), dev)
+    B = int(table.shape[0])
+    if not isinstance(qtabs, torch.Tensor):
+        qtabs = np.ascontiguousarray(qtabs)
+        if qtabs.dtype != np.uint16:
+            raise TypeError("jpeg_reconstruct_u8: host quantisation tables are uint16, got %s" % qtabs.dtype)
+        qtabs = torch.from_numpy(qtabs.view(np.int16)).to(dev)
+    if qtabs.dtype not in (torch.int16, torch.uint16) or tuple(qtabs.shape) != (B, 3, 64) or not qtabs.is_contiguous() \
+            or qtabs.device != dev:
+        raise ValueError("jpeg_reconstruct_u8: qtabs must be a contiguous 16-bit integer [%d, 3, 64] tensor on %s" % (B, dev))
+    if out is None:
+        out = torch.empty((B, 3, Hs, Ws), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, 3, Hs, Ws) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("jpeg_reconstruct_u8: out must be a contiguous uint8 tensor of shape %s on %s" % ((B, 3, Hs, Ws), dev))
+    L = _lib.lib()
+    need = int(L.vr_jpeg_ws_bytes(nbytes))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError("jpeg_reconstruct_u8: the workspace is a contiguous uint8 tensor on %s" % (dev,))
+    _lib.check(L.vr_jpeg_reconstruct_u8(_p(blob), nbytes, _p(table), _p(qtabs), _p(out), B, Hs, Ws, _p(workspace),
+                                        int(workspace.numel()), _stream()), "vr_jpeg_reconstruct_u8")
+    return out

@@ -11,7 +11,8 @@ itself (tests/golden/f20_resample_pil.npz).
 
 What is not here: RandAugment, which sits between the flip and ToTensor, is vitres/rand_augment.py and runs on this stage's output
 (DeviceCropLoader(augment=)).  ColorJitter is not implemented: timm skips it whenever auto_augment is set, so no shipped recipe runs
-it.  Decoding stays on the host.  interpolation='random' (timm picks bilinear or bicubic per sample) is not implemented: one launch
+it.  Decoding is not here either: a loader decodes with PIL and pads (pad_collate_u8), or ships JPEG coefficients that the device turns
+into the same canvases (vitres.data.jpeg_collate / DeviceJpegLoader, vr_jpeg_reconstruct_u8).  interpolation='random' (timm picks bilinear or bicubic per sample) is not implemented: one launch
 has one filter.
 """
 import math
