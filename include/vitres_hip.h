@@ -728,6 +728,72 @@ int vr_jpeg_reconstruct_u8(const void* blob, int64_t blob_bytes, const vr_jpeg_d
 size_t vr_jpeg_ws_bytes(int64_t blob_bytes);
 
 /*
+ * The ragged route through the same two stages: image batches of any size.  The padded entries above take one canvas [B,C,Hs,Ws]
+ * whose sides are the batch maxima, so one large photograph costs every sample its memory, its traffic and -- in vr_resample_u8 --
+ * the launch itself.  Here every sample has planes of its OWN size in one flat uint8 buffer, placed by a device table:
+ *   vr_ragged_plane  off: byte offset of channel 0 in the flat buffer, a multiple of 16; pitch: bytes per row, a multiple of 4 and
+ *                    >= the image's width; rows >= the image's height; channel c starts at off + c * rows * pitch.  Columns between
+ *                    the width and the pitch are zero.  Nothing requires two samples to share a pitch, and the buffer may have gaps.
+ *                    ws_off: vr_resample_ragged_u8 only (below).
+ * The device checks a plane record before anything is addressed through it: off >= 0 and off % 16 == 0, 4 <= pitch <= the launch's
+ * Ws bound and pitch % 4 == 0, 1 <= rows <= the launch's Hs bound, off + C * rows * pitch <= the declared size of the buffer.
+ * vitres.kernels.check_ragged_planes rejects such records -- and planes that overlap -- on the host copy.
+ *
+ * vr_jpeg_reconstruct_ragged_u8: vr_jpeg_reconstruct_u8 with another destination -- the same blob, records, record checks, raw
+ * records, qtabs, arithmetic (the same device code) and workspace rule; Hs and Ws (both <= 8192, Ws % 4 == 0) bound every plane's rows
+ * and pitch as they bound every image's sides.  For every image whose plane record passes and holds it (pitch >= width, rows >=
+ * height) EVERY byte of its three planes is written, rows * pitch each: the pixels, zero outside the image, zero everywhere if the
+ * JPEG record fails its check; grayscale in all three.  Nothing else is written: bytes of dst between planes keep their values, and a
+ * sample whose plane record fails, or is too small for its image, has nothing written at all.  No record of either table, valid or
+ * not, makes the launches address anything outside blob, dst (dst_bytes) or the workspace.
+ * VR_EINVAL: a null pointer, a non-positive size, a workspace that is missing, too small, or one of blob / dst, dst == blob;
+ * VR_EUNSUPPORTED: Ws % 4, B > 65535, Hs or Ws above 8192; VR_EALIGN: blob, workspace or dst not 16-byte, planes not 8-byte, descs not
+ * 4-byte, qtabs not 2-byte aligned.  Checked before anything is launched.
+ *
+ * vr_resample_ragged_u8: vr_resample_u8's arithmetic, boxes (the same vr_resample_box table, read on the device), window and mirror
+ * semantics and output [B,C,So_h,So_w], bit for bit, from ragged planes of C channels -- with NO limit on the scale: any box with
+ * 1 <= w, h <= 8192 inside its own sample's pitch x rows, to any So_h, So_w (So_w % 4 == 0).  Two launches through a global
+ * workspace, so that no source row is resampled twice:
+ *   horizontal  one workgroup per (sample, block of 32 of the crop's source rows the window's vertical taps touch), all channels:
+ *               the horizontal coefficients in LDS a chunk of output columns at a time (a column of the widest box has 8193 taps: one
+ *               column then fills the table), row segments staged as aligned dwords, the uint8 intermediate [C][h][So_w] of the sample
+ *               written at workspace + ws_off;
+ *   vertical    one workgroup per (sample, band of 8 output rows): the band's vertical coefficients in LDS, swept in slices when a
+ *               row has more taps than the table holds (h = 8192 to one row: 32769), the intermediate read as dwords, 4 pixels per
+ *               lane and tap, the (mirrored) output written.
+ * PIL's pass order is followed: Image.resize runs the VERTICAL pass first on an image (here: a crop) with h > 100 w and oh < h, the
+ * 8-bit intermediate then being w x oh; such a crop (at most 81 wide) skips the first launch and is done whole by the second
+ * (vr_resample_u8 does not do this and differs from PIL for such crops).
+ * Hs bounds every plane's rows, Ws every pitch: they size the grids, the check above and -- through the most taps a box inside them
+ * can have -- the kernels' LDS, which stays within the 64 KiB a launch gets without raising its limit whatever they are.  workspace: every sample's intermediate is C * h * So_w bytes (h = its box's height) at its record's ws_off, a
+ * multiple of 4 the HOST fills so that the intermediates do not overlap; vr_resample_ragged_ws_bytes(C, total_rows, So_w) =
+ * C * total_rows * So_w rounded up to 16 is what offsets packed over heights that sum to total_rows need -- the sum of the boxes'
+ * heights, or (for tables rewritten under a captured launch) of the planes' rows, which bounds it; never B times the tallest.
+ * The kernels clamp every box into its sample's plane, as vr_resample_u8 clamps into the canvas.  A sample whose plane record
+ * fails the check above, or whose intermediate does not lie inside ws_bytes, gets zeros in its output and nothing is read for it.
+ * `boxes` and `planes` are DEVICE arrays read at run time: a captured launch follows tables rewritten in place.
+ * VR_EINVAL: a null pointer, a non-positive size, C outside 1..4, filter not 2 / 3, a workspace that is missing, smaller than
+ * vr_resample_ragged_ws_bytes(C, 1, So_w), or one of src / out, src == out; VR_EUNSUPPORTED: So_w % 4, Ws % 4, B > 65535;
+ * VR_EALIGN: src or workspace not 16-byte, planes not 8-byte, out or boxes not 4-byte aligned.  Checked before anything is launched.
+ */
+typedef struct vr_ragged_plane {
+    int64_t off;               /* byte offset of channel 0 in the flat buffer, a multiple of 16                        */
+    int32_t pitch;             /* bytes per row: a multiple of 4, >= the image's width                                 */
+    int32_t rows;              /* rows per channel, >= the image's height                                              */
+    int64_t ws_off;            /* vr_resample_ragged_u8: byte offset of the sample's intermediate in the workspace     */
+    int32_t reserved[2];
+} vr_ragged_plane;             /* 32 bytes */
+int vr_jpeg_reconstruct_ragged_u8(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs /* device, [B] */,
+                                  const uint16_t* qtabs /* device, [B,3,64] */, uint8_t* dst, int64_t dst_bytes,
+                                  const vr_ragged_plane* planes /* device, [B] */, int32_t B, int32_t Hs, int32_t Ws,
+                                  void* workspace, size_t ws_bytes, vr_stream_t stream);
+int vr_resample_ragged_u8(const uint8_t* src, int64_t src_bytes, const vr_ragged_plane* planes /* device, [B] */,
+                          const vr_resample_box* boxes /* device, [B] */, uint8_t* out /* [B,C,So_h,So_w] */, int32_t B, int32_t C,
+                          int32_t Hs, int32_t Ws, int32_t So_h, int32_t So_w, int32_t filter, void* workspace, size_t ws_bytes,
+                          vr_stream_t stream);
+size_t vr_resample_ragged_ws_bytes(int32_t C, int64_t total_rows, int32_t So_w);
+
+/*
  * patch_output_type == 'avg' (nets/vit_sr_supernet.py:447-449: patch_features.mean(dim=1) before patch_head):
  * out[b, c] = mean over tokens n in [first, N) of y[b, n, c]; backward writes dy[b, n, c] = dmean[b, c] / (N - first) for those
  * tokens.  All tensors in `dtype`, fp32 accumulation.

@@ -12,8 +12,11 @@
 //                         from the blob.  Threads outside the image -- and every thread of an image whose record fails the
 //                         device's own check -- store zeros, so the launch writes every byte of the canvas.
 // Every record is validated against blob_bytes, Hs, Ws and the limits before anything is read through it, by both kernels.
+// vr_jpeg_reconstruct_ragged_u8 is the same entry with another destination: launch 1 unchanged, then jpeg_place_ragged_kernel, which
+// writes every image's planes of its OWN size (vr_ragged_plane, ragged.h) in a flat buffer -- the pixels come from the same jp_quad.
 #include "common.h"
 #include "../../include/vitres_hip.h"
+#include "ragged.h"
 
 namespace {
 
@@ -160,19 +163,12 @@ __device__ __forceinline__ void jp_chroma4(const uint32_t* row32, int nd, int i,
 
 __device__ __forceinline__ uint32_t jp_byte(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
-__global__ __launch_bounds__(JP_THREADS) void jpeg_place_kernel(const uint8_t* __restrict__ blob, long long blob_bytes,
-                                                                const vr_jpeg_desc* __restrict__ descs,
-                                                                const uint8_t* __restrict__ ws, uint8_t* __restrict__ canvas, int Hs,
-                                                                int Ws) {
-    const int b = blockIdx.y, wq = Ws >> 2;
-    const long long quad = (long long)blockIdx.x * JP_THREADS + threadIdx.x;
-    if (quad >= (long long)Hs * wq) return;
-    const int y = (int)(quad / wq), x0 = 4 * (int)(quad - (long long)y * wq);
-    const size_t plane = (size_t)Hs * Ws;
-    uint32_t* out = (uint32_t*)(canvas + (size_t)b * 3 * plane + (size_t)y * Ws + x0);
-    const vr_jpeg_desc d = descs[b];
-    uint32_t R = 0u, G = 0u, B = 0u;
-    if (jp_valid(d, blob_bytes, Hs, Ws) && y < d.height && x0 < d.width) {
+// The four pixels (y, x0 .. x0 + 3) of the image of a record that passed jp_valid, a byte each in R, G, B; zero where outside the
+// image.  Both place kernels -- the padded canvas and the ragged planes -- get their bytes here.
+__device__ __forceinline__ void jp_quad(const uint8_t* __restrict__ blob, const uint8_t* __restrict__ ws, const vr_jpeg_desc& d,
+                                        int y, int x0, uint32_t& R, uint32_t& G, uint32_t& B) {
+    R = G = B = 0u;
+    if (y < d.height && x0 < d.width) {
         const bool raw = d.kind == VR_JPEG_RAW;
         const uint8_t* base = raw ? blob : ws;
         const size_t unit = raw ? 16 : 8;                                    // bytes per offset unit: coefficients are two bytes a sample
@@ -247,9 +243,54 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_place_kernel(const uint8_t* _
             B &= m;
         }
     }
+}
+
+__global__ __launch_bounds__(JP_THREADS) void jpeg_place_kernel(const uint8_t* __restrict__ blob, long long blob_bytes,
+                                                                const vr_jpeg_desc* __restrict__ descs,
+                                                                const uint8_t* __restrict__ ws, uint8_t* __restrict__ canvas, int Hs,
+                                                                int Ws) {
+    const int b = blockIdx.y, wq = Ws >> 2;
+    const long long quad = (long long)blockIdx.x * JP_THREADS + threadIdx.x;
+    if (quad >= (long long)Hs * wq) return;
+    const int y = (int)(quad / wq), x0 = 4 * (int)(quad - (long long)y * wq);
+    const size_t plane = (size_t)Hs * Ws;
+    uint32_t* out = (uint32_t*)(canvas + (size_t)b * 3 * plane + (size_t)y * Ws + x0);
+    const vr_jpeg_desc d = descs[b];
+    uint32_t R = 0u, G = 0u, B = 0u;
+    if (jp_valid(d, blob_bytes, Hs, Ws)) jp_quad(blob, ws, d, y, x0, R, G, B);
     out[0] = R;
     *(uint32_t*)((uint8_t*)out + plane) = G;
     *(uint32_t*)((uint8_t*)out + 2 * plane) = B;
+}
+
+// The ragged form: the sample's three planes of rows x pitch bytes at its record's offset in the flat buffer, every byte of them.
+// A sample whose plane record fails rg_plane_ok, or does not hold the image, has nothing written; an invalid JPEG record zeros.
+constexpr int JP_RAGGED_QUADS = 4;                    // quads per thread at the launch's bounds (the grid strides over a sample's)
+__global__ __launch_bounds__(JP_THREADS) void jpeg_place_ragged_kernel(const uint8_t* __restrict__ blob, long long blob_bytes,
+                                                                       const vr_jpeg_desc* __restrict__ descs,
+                                                                       const uint8_t* __restrict__ ws, uint8_t* __restrict__ dst,
+                                                                       long long dst_bytes,
+                                                                       const vr_ragged_plane* __restrict__ planes, int Hs, int Ws) {
+    const int b = blockIdx.y;
+    const vr_ragged_plane p = planes[b];
+    if (!rg_plane_ok(p, 3, dst_bytes, Hs, Ws)) return;                               // (uniform over the workgroup)
+    const int pq = p.pitch >> 2;
+    const long long quads = (long long)p.rows * pq;
+    if ((long long)blockIdx.x * JP_THREADS >= quads) return;
+    const vr_jpeg_desc d = descs[b];
+    const bool valid = jp_valid(d, blob_bytes, Hs, Ws);
+    if (valid && (d.width > p.pitch || d.height > p.rows)) return;                   // the plane does not hold the image
+    const size_t plane = (size_t)p.rows * p.pitch;
+    uint8_t* base = dst + p.off;
+    for (long long quad = (long long)blockIdx.x * JP_THREADS + threadIdx.x; quad < quads; quad += (long long)gridDim.x * JP_THREADS) {
+        const int y = (int)(quad / pq), x0 = 4 * (int)(quad - (long long)y * pq);
+        uint32_t R = 0u, G = 0u, B = 0u;
+        if (valid) jp_quad(blob, ws, d, y, x0, R, G, B);
+        uint8_t* out = base + (size_t)y * p.pitch + x0;
+        *(uint32_t*)out = R;
+        *(uint32_t*)(out + plane) = G;
+        *(uint32_t*)(out + 2 * plane) = B;
+    }
 }
 
 }  // namespace
@@ -282,6 +323,30 @@ extern "C" int vr_jpeg_reconstruct_u8(const void* blob, int64_t blob_bytes, cons
     hipLaunchKernelGGL(jpeg_place_kernel, dim3((unsigned)((quads + JP_THREADS - 1) / JP_THREADS), B), dim3(JP_THREADS), 0,
                        (hipStream_t)stream, (const uint8_t*)blob, (long long)blob_bytes, descs, (const uint8_t*)workspace, canvas, Hs,
                        Ws);
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
+
+extern "C" int vr_jpeg_reconstruct_ragged_u8(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs, const uint16_t* qtabs,
+                                             uint8_t* dst, int64_t dst_bytes, const vr_ragged_plane* planes, int32_t B, int32_t Hs,
+                                             int32_t Ws, void* workspace, size_t ws_bytes, vr_stream_t stream) {
+    if (!blob || !descs || !qtabs || !dst || !planes || blob_bytes <= 0 || dst_bytes <= 0 || B <= 0 || Hs <= 0 || Ws <= 0)
+        return VR_EINVAL;
+    if (!workspace || ws_bytes < vr_jpeg_ws_bytes(blob_bytes) || workspace == blob || workspace == (void*)dst || (const void*)dst == blob)
+        return VR_EINVAL;
+    if (Ws % 4 || B > 65535 || Hs > JP_MAX_SIDE || Ws > JP_MAX_SIDE) return VR_EUNSUPPORTED;
+    if (((uintptr_t)blob & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)planes & 7)
+        || ((uintptr_t)descs & 3) || ((uintptr_t)qtabs & 1))
+        return VR_EALIGN;
+    const long long most = 3LL * (Ws / 8 + 2) * (Hs / 8 + 2);                        // as the padded entry: Hs, Ws bound every image
+    const unsigned gx = (unsigned)((most + JP_THREADS - 1) / JP_THREADS);
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(gx, B), dim3(JP_THREADS), 0, (hipStream_t)stream, (const uint8_t*)blob,
+                       (long long)blob_bytes, descs, qtabs, (uint8_t*)workspace, Hs, Ws);
+    VR_CHECK_LAUNCH();
+    const long long per = (long long)JP_THREADS * JP_RAGGED_QUADS, quads = (long long)Hs * (Ws / 4);
+    hipLaunchKernelGGL(jpeg_place_ragged_kernel, dim3((unsigned)((quads + per - 1) / per), B), dim3(JP_THREADS), 0, (hipStream_t)stream,
+                       (const uint8_t*)blob, (long long)blob_bytes, descs, (const uint8_t*)workspace, dst, (long long)dst_bytes, planes,
+                       Hs, Ws);
     VR_CHECK_LAUNCH();
     return VR_OK;
 }

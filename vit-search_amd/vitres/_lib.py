@@ -94,6 +94,10 @@ class JpegDesc(ctypes.Structure):
 VR_JPEG_COEF, VR_JPEG_RAW = 0, 1
 
 
+class RaggedPlane(ctypes.Structure):
+    _fields_ = [("off", c_int64), ("pitch", c_int32), ("rows", c_int32), ("ws_off", c_int64), ("reserved", c_int32 * 2)]
+
+
 class JpegInfo(ctypes.Structure):                 # include/vitres_jpeg.h
     _fields_ = [("supported", c_int32), ("width", c_int32), ("height", c_int32), ("ncomp", c_int32), ("hs", c_int32), ("vs", c_int32),
                 ("restart_interval", c_int32), ("blocks", c_int32 * 3), ("bw", c_int32 * 3), ("bh", c_int32 * 3)]
@@ -152,6 +156,9 @@ SYMBOLS = {
     "vr_rand_augment_u8": [c_void_p, c_void_p, c_void_p] + [c_int32] * 4 + [ctypes.c_uint32, c_void_p, ctypes.c_size_t, c_void_p],
     "vr_jpeg_reconstruct_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, ctypes.c_size_t,
                                c_void_p],
+    "vr_jpeg_reconstruct_ragged_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32,
+                                      c_void_p, ctypes.c_size_t, c_void_p],
+    "vr_resample_ragged_u8": [c_void_p, c_int64, c_void_p, c_void_p, c_void_p] + [c_int32] * 7 + [c_void_p, ctypes.c_size_t, c_void_p],
     "vr_token_mean": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_token_mean_bwd": [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p],
     "vr_batchsum": [c_void_p, c_void_p, c_int32, c_int64, c_void_p],
@@ -184,6 +191,7 @@ OTHER_SYMBOLS = {
     "vr_resample_ws_bytes": ([c_int32, c_int32, c_int32], ctypes.c_size_t),
     "vr_rand_augment_ws_bytes": ([c_int32] * 4, ctypes.c_size_t),
     "vr_jpeg_ws_bytes": ([c_int64], ctypes.c_size_t),
+    "vr_resample_ragged_ws_bytes": ([c_int32, c_int64, c_int32], ctypes.c_size_t),
 }
 
 # the host-only library: name -> argtypes, every entry returns int

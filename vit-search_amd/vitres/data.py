@@ -18,6 +18,12 @@ training, the `vr_token_mix_u8` pass of `SwitchTokenMix(input_norm=...)` -- make
   DeviceJpegLoader       those blobs in, the canvases pad_collate_u8 would have made out -- on the device (vr_jpeg_reconstruct_u8:
                          dequantise, inverse DCT, chroma upsampling, colour conversion, placement): what DeviceCropLoader takes.
 
+  ragged_collate_u8      pad_collate_u8's ragged sibling: every image in planes of its OWN size in one flat buffer (no canvas of the
+                         batch maxima), with the plane table vr_resample_ragged_u8 reads.  DeviceCropLoader takes its batches too.
+  RaggedCanvas           what DeviceJpegLoader(ragged=True) yields in the canvas's place: the flat device buffer and its plane table
+                         (vr_jpeg_reconstruct_ragged_u8).  Memory, traffic and the resample's cost then follow the batch's pixels,
+                         not B times its largest image, and no image is too large for the crop (sides up to 8192).
+
 What is not here: the entropy decoding of JPEG stays on host cores (in the loader's workers); progressive, arithmetic-coded and
 non-JPEG files are decoded there entirely, by PIL.  ColorJitter is not implemented: timm skips it
 whenever auto_augment is set, so no shipped recipe runs it.  Random
@@ -141,6 +147,48 @@ def pad_collate_u8(samples):
     return torch.from_numpy(canvas), torch.from_numpy(sizes), labels
 
 
+def ragged_collate_u8(samples):
+    """pad_collate_u8 without the canvas: a list of (HWC uint8 array, label) -- decoded images of any sizes, one channel count --
+    into (flat uint8 [n], planes int32 [B,8], sizes int32 [B,2] of (h, w), labels int64 [B]), plain tensors so that pin_memory=True
+    works.  Every image lies in C planes of its own size (kernels.ragged_layout: pitch = its width rounded up to 4, rows = its
+    height, channel c at off + c * rows * pitch, every sample on a multiple of 16 bytes); pad columns and the bytes between
+    samples are zero.  The first reserved word of every record notes the channel count (the device ignores it).  What a DataLoader(collate_fn=ragged_collate_u8) hands to DeviceCropLoader."""
+    if not samples:
+        raise ValueError("ragged_collate_u8: an empty batch")
+    images = [np.asarray(img) for img, _ in samples]
+    for img in images:
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != images[0].shape[2] or 0 in img.shape:
+            raise TypeError("ragged_collate_u8 takes non-empty HWC uint8 arrays of one channel count, got %s %s" % (img.dtype, img.shape))
+    C = images[0].shape[2]
+    sizes = np.array([img.shape[:2] for img in images], dtype=np.int32)
+    planes, nbytes = K.ragged_layout(sizes, C)
+    planes["reserved"][:, 0] = C              # (for DeviceCropLoader: the device ignores the reserved words)
+    flat = np.zeros(nbytes, dtype=np.uint8)
+    for img, p in zip(images, planes):
+        h, w = img.shape[:2]
+        off, pitch = int(p["off"]), int(p["pitch"])
+        flat[off:off + C * h * pitch].reshape(C, h, pitch)[:, :, :w] = img.transpose(2, 0, 1)
+    labels = torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
+    return (torch.from_numpy(flat), torch.from_numpy(planes.view(np.int32).reshape(len(images), K.RAGGED_PLANE_INTS)),
+            torch.from_numpy(sizes), labels)
+
+
+class RaggedCanvas:
+    """A batch of images in ragged planes on the device: .flat (uint8 [n]), .planes (the device table, int32 [B,8]), .host_planes
+    (its host copy, a kernels.ragged_planes array) and .channels.  What DeviceJpegLoader(ragged=True) yields where the padded form
+    yields a canvas; DeviceCropLoader takes either."""
+
+    def __init__(self, flat, planes, host_planes, channels=3):
+        self.flat, self.planes, self.host_planes, self.channels = flat, planes, host_planes, int(channels)
+
+    def plane(self, b, size=None):
+        """Sample b's planes as a [C, rows, pitch] view of .flat ([C, h, w] with size=(h, w))."""
+        p = self.host_planes[b]
+        off, rows, pitch = int(p["off"]), int(p["rows"]), int(p["pitch"])
+        view = self.flat[off:off + self.channels * rows * pitch].view(self.channels, rows, pitch)
+        return view if size is None else view[:, :int(size[0]), :int(size[1])]
+
+
 class DeviceCropLoader:
     """Over a loader of (canvas uint8 [B,C,Hs,Ws], sizes [B,2], labels) host batches (pad_collate_u8): yields
     (uint8 [B,C,S,S] on `device`, labels on `device`), the canvas cropped, resized and mirrored by vr_resample_u8 with the boxes
@@ -150,10 +198,15 @@ class DeviceCropLoader:
     uploaded.  The output is what DevicePrefetchLoader, SwitchTokenMix(input_norm=), Mixup(input_norm=) and ResidentU8Batches take;
     nothing is normalised here.  augment=RandAugment(...) (vitres.rand_augment: .draw(B), .fill, .size): the batch's op table is drawn
     after its boxes, copied with them, and vr_rand_augment_u8 runs on the cropped batch (3 channels); augment=None adds nothing.
+    A loader of ragged batches -- (flat, planes, sizes, labels) of ragged_collate_u8, or (RaggedCanvas, sizes, labels) of
+    DeviceJpegLoader(ragged=True) -- is taken as well: the same draws, checked against every sample's own plane, through
+    vr_resample_ragged_u8, whose workspace is kept and grown as batches need.  The yielded batches are the same bytes wherever the
+    padded route works; the ragged one has no image too large for it.
     __len__, .sampler and .dataset are the wrapped loader's."""
 
     def __init__(self, loader, transform, device, augment=None):
         self.loader, self.transform, self.device, self.augment = loader, transform, torch.device(device), augment
+        self._rws = None                      # the ragged resample's workspace
         if augment is not None:
             size = (transform.size, transform.size) if isinstance(transform.size, int) else tuple(transform.size)
             if tuple(augment.size) != size:
@@ -197,13 +250,66 @@ class DeviceCropLoader:
     def __iter__(self):
         side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         ahead = None
-        for canvas, sizes, labels in self.loader:
-            nxt = self._upload(side, canvas, sizes, labels)
+        for batch in self.loader:
+            if len(batch) == 4 or isinstance(batch[0], RaggedCanvas):
+                nxt = (self._hand_over_ragged, self._upload_ragged(side, *batch))
+            else:
+                nxt = (self._hand_over, self._upload(side, *batch))
             if ahead is not None:
-                yield self._hand_over(*ahead)
+                yield ahead[0](*ahead[1])
             ahead = nxt
         if ahead is not None:
-            yield self._hand_over(*ahead)
+            yield ahead[0](*ahead[1])
+
+    def _upload_ragged(self, side, flat, planes, sizes, labels=None):
+        if isinstance(flat, RaggedCanvas):    # (already on the device: DeviceJpegLoader(ragged=True) yields (canvas, sizes, labels))
+            flat, planes, sizes, labels, C = flat.flat, flat.host_planes.copy(), planes, sizes, flat.channels
+        else:
+            if flat.dtype != torch.uint8 or flat.dim() != 1 or planes.dtype != torch.int32 or planes.dim() != 2:
+                raise TypeError("DeviceCropLoader takes ragged batches as (flat uint8 [n], planes int32 [B,8], sizes, labels) "
+                                "(ragged_collate_u8)")
+            planes = np.ascontiguousarray(planes.numpy()).view(K.RAGGED_PLANE_DTYPE).reshape(-1).copy()
+            C = int(planes["reserved"][0, 0]) or 3   # (ragged_collate_u8's note of the channel count: a flat buffer does not say)
+        B = planes.shape[0]
+        sizes = np.asarray(sizes, dtype=np.int64)
+        K.check_ragged_planes(planes, C, int(flat.numel()), sizes, "DeviceCropLoader")
+        size = self.transform.size
+        table = K.check_ragged_boxes(self.transform.draw(sizes), planes, size)
+        So_w = size if isinstance(size, int) else size[1]
+        need = K.ragged_ws_offsets(planes, C, So_w, table[:, 3])
+        bounds = K.ragged_bounds(planes)
+        pinned = side is not None
+        host = torch.empty(table.shape, dtype=torch.int32, pin_memory=pinned)
+        host.numpy()[...] = table
+        hplanes = torch.empty((B, K.RAGGED_PLANE_INTS), dtype=torch.int32, pin_memory=pinned)
+        hplanes.numpy()[...] = planes.view(np.int32).reshape(B, K.RAGGED_PLANE_INTS)
+        ops = None
+        if self.augment is not None:
+            ra = K.check_ra_table(self.augment.draw(B), B)
+            ops = torch.empty(ra.shape, dtype=torch.int32, pin_memory=pinned)
+            ops.numpy()[...] = ra
+        if side is None:
+            return (flat.to(self.device), hplanes.to(self.device), host.to(self.device), labels.to(self.device), C, need, bounds, None,
+                    None if ops is None else ops.to(self.device))
+        with torch.cuda.stream(side):
+            moved = flat if flat.is_cuda else flat.to(self.device, non_blocking=True)
+            hplanes, host, labels = (t.to(self.device, non_blocking=True) for t in (hplanes, host, labels))
+            ops = None if ops is None else ops.to(self.device, non_blocking=True)
+            return moved, hplanes, host, labels, C, need, bounds, side.record_event(), ops
+
+    def _hand_over_ragged(self, flat, planes, table, labels, C, need, bounds, copied, ops=None):
+        if copied is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(copied)
+            for t in (flat, planes, table, labels) + (() if ops is None else (ops,)):
+                t.record_stream(cur)
+        if self._rws is None or self._rws.numel() < need:
+            self._rws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        crop = K.resample_ragged_u8(flat, planes, table, C, self.transform.size, self.transform.filter, workspace=self._rws,
+                                    bounds=bounds)
+        if ops is None:
+            return crop, labels
+        return K.rand_augment_u8(crop, ops, self.augment.fill), labels
 
     def _hand_over(self, canvas, table, labels, copied, ops=None):
         if copied is not None:
@@ -289,10 +395,13 @@ class DeviceJpegLoader:
     a side stream (the DevicePrefetchLoader pattern); the records are checked against the blob and the canvas on the host copy when
     a batch is uploaded.  The canvases alternate between TWO buffers and the launches share one workspace, all kept and grown as
     batches need: a yielded canvas is valid until the batch after next is requested, which is what a consumer that launches on the
-    current stream -- DeviceCropLoader -- needs.  __len__, .sampler and .dataset are the wrapped loader's."""
+    current stream -- DeviceCropLoader -- needs.  ragged=True: a RaggedCanvas in the canvas's place (vr_jpeg_reconstruct_ragged_u8:
+    every image in planes of its own size, kernels.ragged_layout of the batch's sizes) -- the same pixels in memory that follows
+    the batch's pixels instead of B times its largest image; the two flat buffers alternate and grow in the same way.
+    __len__, .sampler and .dataset are the wrapped loader's."""
 
-    def __init__(self, loader, device):
-        self.loader, self.device = loader, torch.device(device)
+    def __init__(self, loader, device, ragged=False):
+        self.loader, self.device, self.ragged = loader, torch.device(device), bool(ragged)
         self._canvas, self._ws, self._turn = [None, None], None, 0
 
     def __len__(self):
@@ -311,11 +420,22 @@ class DeviceJpegLoader:
             raise TypeError("DeviceJpegLoader takes jpeg_collate batches (blob uint8 [n], descs int32 [B,16], ...)")
         Hs, Ws = ((int(v) + 3) // 4 * 4 for v in np.asarray(sizes).max(axis=0))
         K.check_jpeg_table(descs.numpy(), int(blob.numel()), Hs, Ws)
+        planes = None
+        if self.ragged:
+            layout, nbytes = K.ragged_layout(np.asarray(sizes), 3)
+            table = K.check_ragged_planes(layout, 3, nbytes, np.asarray(sizes), "DeviceJpegLoader")
+            dev_table = torch.empty(table.shape, dtype=torch.int32, pin_memory=side is not None)
+            dev_table.numpy()[...] = table
+            planes = (layout, nbytes, dev_table)
         if side is None:                      # (not a GPU: nothing to overlap; the kernel itself has no CPU form)
-            return blob.to(self.device), descs.to(self.device), qtabs.to(self.device), sizes, labels, Hs, Ws, None
+            if planes is not None:
+                planes = planes[:2] + (planes[2].to(self.device),)
+            return blob.to(self.device), descs.to(self.device), qtabs.to(self.device), sizes, labels, Hs, Ws, None, planes
         with torch.cuda.stream(side):
             blob, descs, qtabs = (t.to(self.device, non_blocking=True) for t in (blob, descs, qtabs))
-            return blob, descs, qtabs, sizes, labels, Hs, Ws, side.record_event()
+            if planes is not None:
+                planes = planes[:2] + (planes[2].to(self.device, non_blocking=True),)
+            return blob, descs, qtabs, sizes, labels, Hs, Ws, side.record_event(), planes
 
     def __iter__(self):
         side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
@@ -333,14 +453,21 @@ class DeviceJpegLoader:
             held = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return held
 
-    def _hand_over(self, blob, descs, qtabs, sizes, labels, Hs, Ws, copied):
+    def _hand_over(self, blob, descs, qtabs, sizes, labels, Hs, Ws, copied, planes=None):
         if copied is not None:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(copied)
-            for t in (blob, descs, qtabs):    # (allocated on the side stream, used on this one)
+            for t in (blob, descs, qtabs) + (() if planes is None else (planes[2],)):  # (allocated on the side stream, used on this one)
                 t.record_stream(cur)
         B = int(descs.shape[0])
         turn, self._turn = self._turn, self._turn ^ 1
+        if planes is not None:
+            layout, nbytes, table = planes
+            self._canvas[turn] = self._buffer(self._canvas[turn], nbytes)
+            self._ws = self._buffer(self._ws, K.jpeg_ws_bytes(blob.numel()))
+            flat = self._canvas[turn][:nbytes]
+            K.jpeg_reconstruct_ragged_u8(blob, descs, qtabs, table, dst=flat, workspace=self._ws, bounds=K.ragged_bounds(layout))
+            return RaggedCanvas(flat, table, layout, 3), sizes, labels
         self._canvas[turn] = self._buffer(self._canvas[turn], B * 3 * Hs * Ws)
         self._ws = self._buffer(self._ws, K.jpeg_ws_bytes(blob.numel()))
         canvas = self._canvas[turn][:B * 3 * Hs * Ws].view(B, 3, Hs, Ws)

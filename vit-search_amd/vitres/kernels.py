@@ -1405,3 +1405,255 @@ def jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=None, workspace=None):
     _lib.check(L.vr_jpeg_reconstruct_u8(_p(blob), nbytes, _p(table), _p(qtabs), _p(out), B, Hs, Ws, _p(workspace),
                                         int(workspace.numel()), _stream()), "vr_jpeg_reconstruct_u8")
     return out
+
+
+# ---- the ragged route: planes of every sample's own size in one flat buffer (vr_jpeg_reconstruct_ragged_u8, vr_resample_ragged_u8) -------
+# one record of the device table (vr_ragged_plane, 32 bytes = 8 int32)
+RAGGED_PLANE_DTYPE = np.dtype([("off", "<i8"), ("pitch", "<i4"), ("rows", "<i4"), ("ws_off", "<i8"), ("reserved", "<i4", (2,))])
+RAGGED_PLANE_INTS = ctypes.sizeof(_lib.RaggedPlane) // 4
+assert RAGGED_PLANE_DTYPE.itemsize == ctypes.sizeof(_lib.RaggedPlane) == 32 and RAGGED_PLANE_INTS == 8
+RAGGED_MAX_SIDE = 8192
+RAGGED_ALIGN = 16                          # a sample's offset in the flat buffer
+
+
+def ragged_planes(B):
+    """A zeroed host table of B records (RAGGED_PLANE_DTYPE: off, pitch, rows, ws_off)."""
+    return np.zeros(B, dtype=RAGGED_PLANE_DTYPE)
+
+
+def ragged_layout(sizes, C=3):
+    """(planes, nbytes): the packed layout of images of `sizes` [B,2] (h, w) with C channels -- pitch = the width rounded up to 4,
+    rows = the height, every sample on the next multiple of 16; nbytes = the flat buffer's size (a multiple of 16)."""
+    sizes = np.asarray(sizes, dtype=np.int64)
+    if sizes.ndim != 2 or sizes.shape[1] != 2 or sizes.shape[0] < 1 or (sizes < 1).any():
+        raise ValueError("ragged_layout: sizes must hold one positive (h, w) per sample, got shape %s" % (sizes.shape,))
+    planes = ragged_planes(sizes.shape[0])
+    pitch = (sizes[:, 1] + 3) // 4 * 4
+    span = (int(C) * sizes[:, 0] * pitch + RAGGED_ALIGN - 1) // RAGGED_ALIGN * RAGGED_ALIGN
+    ends = np.cumsum(span)
+    planes["off"], planes["pitch"], planes["rows"] = ends - span, pitch, sizes[:, 0]
+    return planes, int(ends[-1])
+
+
+def _ragged_table(planes, what):
+    planes = np.asarray(planes)
+    if planes.dtype != RAGGED_PLANE_DTYPE:
+        if planes.dtype != np.int32 or planes.ndim != 2 or planes.shape[1] != RAGGED_PLANE_INTS:
+            raise ValueError("%s: the plane table must be a ragged_planes array or int32 [B, %d], got %s %s" % (
+                what, RAGGED_PLANE_INTS, planes.dtype, planes.shape))
+        planes = np.ascontiguousarray(planes).view(RAGGED_PLANE_DTYPE).reshape(-1)
+    if planes.ndim != 1 or planes.shape[0] < 1:
+        raise ValueError("%s: the plane table must hold one record per sample, got shape %s" % (what, planes.shape))
+    return np.ascontiguousarray(planes)
+
+
+def ragged_bounds(planes):
+    """(Hs, Ws): the largest rows and pitch of a host plane table -- the bounds a launch over it declares."""
+    planes = _ragged_table(planes, "ragged_bounds")
+    return int(planes["rows"].max()), int(planes["pitch"].max())
+
+
+def check_ragged_planes(planes, C, nbytes, sizes=None, what="vr_resample_ragged_u8"):
+    """planes (RAGGED_PLANE_DTYPE [B], or int32 [B, 8]) as the contiguous int32 [B, 8] array the device reads, with every record
+    checked as the device checks it -- off >= 0 and a multiple of 16, pitch a multiple of 4, 4 <= pitch, 1 <= rows, both at most
+    8192, the C planes inside the nbytes of the flat buffer -- and, beyond that, no two samples overlapping and (sizes [B,2] of
+    (h, w) given) every plane holding its image: pitch >= w, rows >= h.  The device writes zeros / nothing for a bad record and
+    cannot report it, so the host copy is what is checked: RuntimeError VR_EINVAL, before any launch."""
+    planes = _ragged_table(planes, what)
+    B = planes.shape[0]
+    off, pitch, rows = (planes[k].astype(np.int64) for k in ("off", "pitch", "rows"))
+    bad = (off < 0) | (off % RAGGED_ALIGN != 0) | (pitch < 4) | (pitch % 4 != 0) | (pitch > RAGGED_MAX_SIDE) | (rows < 1) \
+        | (rows > RAGGED_MAX_SIDE)
+    size = int(C) * rows * pitch
+    bad |= off + size > int(nbytes)
+    if sizes is not None:
+        sizes = np.asarray(sizes, dtype=np.int64)
+        if sizes.shape != (B, 2):
+            raise ValueError("%s: sizes must hold one (h, w) per plane record, got shape %s" % (what, sizes.shape))
+        bad |= (sizes[:, 0] < 1) | (sizes[:, 1] < 1) | (sizes[:, 0] > rows) | (sizes[:, 1] > pitch)
+    if not bad.any():
+        order = np.argsort(off, kind="stable")
+        over = off[order][:-1] + size[order][:-1] > off[order][1:]
+        bad[order[1:][over]] = True
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise RuntimeError("%s failed: %s: sample %d: the plane record off=%d pitch=%d rows=%d is not one the kernel takes for %d "
+                           "channels in a %d-byte buffer%s (or it overlaps another)" % (
+                               what, _lib._ERR[-1], i, off[i], pitch[i], rows[i], C, nbytes,
+                               "" if sizes is None else " and a %d x %d image" % (sizes[i, 0], sizes[i, 1])))
+    return planes.view(np.int32).reshape(B, RAGGED_PLANE_INTS)
+
+
+def check_ragged_boxes(boxes, planes, out_size, what="vr_resample_ragged_u8"):
+    """check_resample_boxes against every sample's OWN plane: w, h >= 1 (at most 8192), the box inside pitch x rows of its record,
+    the window inside (ow, oh).  Returns the contiguous int32 [B, 12] table; RuntimeError VR_EINVAL for the first bad row."""
+    So_h, So_w = _out_size(out_size)
+    planes = _ragged_table(planes, what)
+    B = planes.shape[0]
+    boxes = np.asarray(boxes)
+    if boxes.ndim != 2 or boxes.shape[0] != B or boxes.shape[1] not in (len(RESAMPLE_BOX_FIELDS), RESAMPLE_BOX_INTS):
+        raise ValueError("%s: the box table has shape %s, expected (%d, %d)" % (what, boxes.shape, B, RESAMPLE_BOX_INTS))
+    table = resample_boxes(B)
+    table[:, :boxes.shape[1]] = boxes
+    x0, y0, w, h, ow, oh, wx, wy = (table[:, i].astype(np.int64) for i in range(8))
+    pitch, rows = planes["pitch"].astype(np.int64), planes["rows"].astype(np.int64)
+    bad = ((w < 1) | (h < 1) | (w > RAGGED_MAX_SIDE) | (h > RAGGED_MAX_SIDE) | (x0 < 0) | (y0 < 0) | (x0 + w > pitch) | (y0 + h > rows)
+           | (wx < 0) | (wy < 0) | (wx + So_w > ow) | (wy + So_h > oh))
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise RuntimeError("%s failed: %s: sample %d: the box x0=%d y0=%d w=%d h=%d must lie inside its own %d x %d plane and the "
+                           "%d x %d window at (%d, %d) inside the resized %d x %d image" % (
+                               what, _lib._ERR[-1], i, x0[i], y0[i], w[i], h[i], rows[i], pitch[i], So_h, So_w, wy[i], wx[i], oh[i],
+                               ow[i]))
+    return table
+
+
+def resample_ragged_ws_bytes(C, total_rows, So_w):
+    """vr_resample_ragged_ws_bytes: the workspace intermediates packed over heights that sum to total_rows need."""
+    C, total_rows, So_w = int(C), int(total_rows), int(So_w)
+    return (C * total_rows * So_w + 15) & ~15 if min(C, total_rows, So_w) > 0 else 0
+
+
+def ragged_ws_offsets(planes, C, So_w, heights=None):
+    """Fill the ws_off of a host plane table IN PLACE -- the samples' intermediates [C][height][So_w] packed one after another -- and
+    return the workspace bytes they need (resample_ragged_ws_bytes of the heights' sum).  heights: the boxes' heights [B]; None: the
+    planes' rows, which bound them (for tables rewritten under a captured launch)."""
+    if planes.dtype != RAGGED_PLANE_DTYPE:
+        raise ValueError("ragged_ws_offsets fills a ragged_planes array, got %s" % planes.dtype)
+    heights = planes["rows"].astype(np.int64) if heights is None else np.asarray(heights, dtype=np.int64)
+    if heights.shape != planes.shape or (heights < 1).any():
+        raise ValueError("ragged_ws_offsets: one positive height per sample expected")
+    span = int(C) * heights * int(So_w)
+    planes["ws_off"] = np.cumsum(span) - span
+    return resample_ragged_ws_bytes(C, int(heights.sum()), So_w)
+
+
+def _flat_u8(t, what):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous():
+        raise TypeError("%s: a contiguous 1-D uint8 tensor expected" % what)
+    return t
+
+
+def jpeg_reconstruct_ragged_u8(blob, descs, qtabs, planes, dst=None, dst_bytes=None, workspace=None, bounds=None):
+    """vr_jpeg_reconstruct_ragged_u8: jpeg_reconstruct_u8 into ragged planes -- every image's three planes (rows x pitch bytes each,
+    zero outside the image) at its record's place in the flat uint8 buffer dst, bit for bit the bytes of the padded canvas inside
+    the image; bytes of dst outside the planes keep their values.  planes: a host table (ragged_planes / ragged_layout; checked
+    against the buffer and the records' sizes, then uploaded) or an int32 [B, 8] DEVICE tensor the caller has checked, with
+    bounds=(Hs, Ws) >= every record's rows and pitch.  dst: None (a zeroed buffer just large enough is made) or a flat uint8 device
+    tensor, of which dst_bytes (default: all) are declared to the kernel.  descs, qtabs, workspace: as jpeg_reconstruct_u8.
+    Returns dst."""
+    _flat_u8(blob, "jpeg_reconstruct_ragged_u8: blob")
+    _p(blob)
+    dev, nbytes = blob.device, int(blob.numel())
+    host_planes = None if isinstance(planes, torch.Tensor) else _ragged_table(planes, "vr_jpeg_reconstruct_ragged_u8")
+    if dst is None:
+        if host_planes is None:
+            raise ValueError("jpeg_reconstruct_ragged_u8: with a device plane table the destination must be given")
+        end = (host_planes["off"].astype(np.int64) + 3 * host_planes["rows"].astype(np.int64) * host_planes["pitch"]).max()
+        dst = torch.zeros(max(int(end), 1), dtype=torch.uint8, device=dev)
+    _flat_u8(dst, "jpeg_reconstruct_ragged_u8: dst")
+    if dst.device != dev:
+        raise ValueError("jpeg_reconstruct_ragged_u8: dst must be on %s" % (dev,))
+    dst_bytes = int(dst.numel()) if dst_bytes is None else int(dst_bytes)
+    if not 0 < dst_bytes <= dst.numel():
+        raise ValueError("jpeg_reconstruct_ragged_u8: dst_bytes must be within the %d bytes of dst" % dst.numel())
+    if host_planes is not None:
+        Hs, Ws = ragged_bounds(host_planes) if bounds is None else (int(v) for v in bounds)
+    elif bounds is None:
+        raise ValueError("jpeg_reconstruct_ragged_u8: a device plane table needs bounds=(Hs, Ws)")
+    else:
+        Hs, Ws = (int(v) for v in bounds)
+    if isinstance(descs, torch.Tensor):
+        if descs.dtype != torch.int32 or descs.dim() != 2 or descs.shape[1] != JPEG_DESC_INTS or not descs.is_contiguous() \
+                or descs.device != dev:
+            raise ValueError("jpeg_reconstruct_ragged_u8: a device record table must be a contiguous int32 [B, %d] tensor on %s" % (
+                JPEG_DESC_INTS, dev))
+        table, sizes = descs, None
+    else:
+        host_descs = check_jpeg_table(descs, nbytes, max(Hs, 1), max(Ws, 1), "vr_jpeg_reconstruct_ragged_u8")
+        table = _upload_i32(host_descs, dev)
+        sizes = host_descs[:, [2, 1]]                                        # (height, width)
+    B = int(table.shape[0])
+    if host_planes is not None:
+        if host_planes.shape[0] != B:
+            raise ValueError("jpeg_reconstruct_ragged_u8: %d plane records for %d images" % (host_planes.shape[0], B))
+        ptable = _upload_i32(check_ragged_planes(host_planes, 3, dst_bytes, sizes, "vr_jpeg_reconstruct_ragged_u8"), dev)
+    else:
+        if planes.dtype != torch.int32 or tuple(planes.shape) != (B, RAGGED_PLANE_INTS) or not planes.is_contiguous() \
+                or planes.device != dev:
+            raise ValueError("jpeg_reconstruct_ragged_u8: a device plane table must be a contiguous int32 [%d, %d] tensor on %s" % (
+                B, RAGGED_PLANE_INTS, dev))
+        ptable = planes
+    if not isinstance(qtabs, torch.Tensor):
+        qtabs = np.ascontiguousarray(qtabs)
+        if qtabs.dtype != np.uint16:
+            raise TypeError("jpeg_reconstruct_ragged_u8: host quantisation tables are uint16, got %s" % qtabs.dtype)
+        qtabs = torch.from_numpy(qtabs.view(np.int16)).to(dev)
+    if qtabs.dtype not in (torch.int16, torch.uint16) or tuple(qtabs.shape) != (B, 3, 64) or not qtabs.is_contiguous() \
+            or qtabs.device != dev:
+        raise ValueError("jpeg_reconstruct_ragged_u8: qtabs must be a contiguous 16-bit integer [%d, 3, 64] tensor on %s" % (B, dev))
+    L = _lib.lib()
+    need = int(L.vr_jpeg_ws_bytes(nbytes))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError("jpeg_reconstruct_ragged_u8: the workspace is a contiguous uint8 tensor on %s" % (dev,))
+    _lib.check(L.vr_jpeg_reconstruct_ragged_u8(_p(blob), nbytes, _p(table), _p(qtabs), _p(dst), dst_bytes, _p(ptable), B, Hs, Ws,
+                                               _p(workspace), int(workspace.numel()), _stream()), "vr_jpeg_reconstruct_ragged_u8")
+    return dst
+
+
+def resample_ragged_u8(src, planes, boxes, C, out_size, filter, out=None, workspace=None, src_bytes=None, bounds=None):
+    """vr_resample_ragged_u8: resample_u8 -- the same boxes, arithmetic, window and mirror, bit for bit PIL's -- from ragged planes of
+    C channels in the flat uint8 device buffer src, with no limit on the scale: any box with sides up to 8192 inside its own plane,
+    to any out_size (So_w % 4 == 0).  Returns uint8 [B,C,So_h,So_w].
+    planes, boxes: host tables (ragged_planes / int arrays) -- checked (check_ragged_planes, check_ragged_boxes), the intermediates
+    laid out over the boxes' heights (ragged_ws_offsets) and both uploaded from pinned memory without a host wait -- or int32 DEVICE
+    tensors [B, 8] and [B, 12] the caller has checked and laid out, which may be rewritten in place between replays of a captured
+    launch; then workspace and bounds=(Hs, Ws) >= every record's rows and pitch must be given.  Host and device tables do not mix.
+    workspace: a uint8 device tensor (None: taken from torch's allocator; a host-table call raises ValueError if a given one is too
+    small); src_bytes: how much of src is declared to the kernel (default: all)."""
+    _flat_u8(src, "resample_ragged_u8: src")
+    _p(src)
+    dev, C = src.device, int(C)
+    So_h, So_w = _out_size(out_size)
+    code = _resample_filter(filter)
+    src_bytes = int(src.numel()) if src_bytes is None else int(src_bytes)
+    if not 0 < src_bytes <= src.numel():
+        raise ValueError("resample_ragged_u8: src_bytes must be within the %d bytes of src" % src.numel())
+    if isinstance(planes, torch.Tensor) != isinstance(boxes, torch.Tensor):
+        raise ValueError("resample_ragged_u8: planes and boxes are both host tables or both device tensors")
+    L = _lib.lib()
+    if isinstance(planes, torch.Tensor):
+        B = int(planes.shape[0])
+        if planes.dtype != torch.int32 or planes.dim() != 2 or planes.shape[1] != RAGGED_PLANE_INTS or not planes.is_contiguous() \
+                or planes.device != dev or boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, RESAMPLE_BOX_INTS) \
+                or not boxes.is_contiguous() or boxes.device != dev:
+            raise ValueError("resample_ragged_u8: device tables must be contiguous int32 [B, %d] and [B, %d] tensors on %s" % (
+                RAGGED_PLANE_INTS, RESAMPLE_BOX_INTS, dev))
+        if workspace is None or bounds is None:
+            raise ValueError("resample_ragged_u8: device tables need workspace= and bounds=(Hs, Ws)")
+        Hs, Ws = (int(v) for v in bounds)
+        ptable, btable = planes, boxes
+    else:
+        host = _ragged_table(planes, "vr_resample_ragged_u8").copy()
+        B = host.shape[0]
+        check_ragged_planes(host, C, src_bytes, None, "vr_resample_ragged_u8")
+        hb = check_ragged_boxes(boxes, host, (So_h, So_w))
+        need = ragged_ws_offsets(host, C, So_w, hb[:, 3]) if 1 <= C <= 4 and So_w > 0 else 16
+        Hs, Ws = ragged_bounds(host) if bounds is None else (int(v) for v in bounds)
+        if workspace is None:
+            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        elif isinstance(workspace, torch.Tensor) and workspace.numel() < need:
+            raise ValueError("resample_ragged_u8: the workspace has %d bytes, the batch needs %d" % (workspace.numel(), need))
+        ptable = _upload_i32(host.view(np.int32).reshape(B, RAGGED_PLANE_INTS), dev)
+        btable = _upload_i32(hb, dev)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError("resample_ragged_u8: the workspace is a contiguous uint8 tensor on %s" % (dev,))
+    if out is None:
+        out = torch.empty((B, C, So_h, So_w), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, C, So_h, So_w) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("resample_ragged_u8: out must be a contiguous uint8 tensor of shape %s on %s" % ((B, C, So_h, So_w), dev))
+    _lib.check(L.vr_resample_ragged_u8(_p(src), src_bytes, _p(ptable), _p(btable), _p(out), B, C, Hs, Ws, So_h, So_w, code,
+                                       _p(workspace), int(workspace.numel()), _stream()), "vr_resample_ragged_u8")
+    return out
