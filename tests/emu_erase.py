@@ -72,19 +72,27 @@ def install(monkeypatch):
         calls.append(dict(what="mixup_u8_erase", erase=erase, mask=mask, erased=xe, result=res))
         return res
 
-    def token_mix_u8_erase(x, labels, draw, patch_len, num_classes, on, off, norm, erase, out=None, targets_out=None,
-                           patch_targets_out=None):
-        assert x.dtype == torch.uint8 and x.dim() == 4
-        check(x, erase)
-        xe, mask = erased(normalized(x, norm), erase)
+    def token_mix(x, labels, draw, patch_len, num_classes, on, off, norm=None, erase=None, out=None, targets_out=None,
+                  patch_targets_out=None):
+        """All three forms by the one name SwitchTokenMix calls: the erased one is logged as before, the others as 'token_mix'."""
+        assert x.dim() == 4 and x.dtype == (torch.float32 if norm is None else torch.uint8) and (erase is None or norm is not None)
+        xe, mask = x if norm is None else normalized(x, norm), None
+        if erase is not None:
+            check(x, erase)
+            xe, mask = erased(xe, erase)
         s0 = off * num_classes                                    # the smoothing whose one-hot values these are (the oracle takes it)
         smoothing = [s for s in (s0, np.nextafter(s0, 0.), np.nextafter(s0, 1.))
                      if s / num_classes == off and 1. - s + s / num_classes == on][0]
         xs, t, pt, _ = O.switch_token_mix(xe, labels, patch_len, num_classes, smoothing, draw=oracle_draw(draw))
         res = (_into(out, xs), _into(targets_out, t), _into(patch_targets_out, pt))
-        calls.append(dict(what="token_mix_u8_erase", erase=erase, mask=mask, erased=xe, result=res))
+        calls.append(dict(what="token_mix" if erase is None else "token_mix_u8_erase", erase=erase, mask=mask, erased=xe, result=res))
         return res
 
-    for fn in (random_erase, normalize_u8_erase, mixup_u8_erase, token_mix_u8_erase):
+    def token_mix_u8_erase(x, labels, draw, patch_len, num_classes, on, off, norm, erase, out=None, targets_out=None,
+                           patch_targets_out=None):
+        assert norm is not None and erase is not None
+        return token_mix(x, labels, draw, patch_len, num_classes, on, off, norm, erase, out, targets_out, patch_targets_out)
+
+    for fn in (random_erase, normalize_u8_erase, mixup_u8_erase, token_mix, token_mix_u8_erase):
         monkeypatch.setattr(K, fn.__name__, fn)
     return calls

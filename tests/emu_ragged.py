@@ -3,6 +3,8 @@ vr_resample_ragged_u8), built on emu_resample and emu_jpeg -- which have no scal
 record checks on its own: nothing here is shared with the product code.
 
 A plane table is a structured array (PLANE: off, pitch, rows, ws_off), or the int32 [B, 8] form the device reads.
+`install(monkeypatch)` puts the emulations -- and the padded ones of emu_resample / emu_jpeg -- in the place of the four entries of
+vitres.kernels that the loaders of vitres.data call: the only function here that touches the product.
 """
 import os
 
@@ -182,3 +184,36 @@ def golden_jpeg_big():
 def repack_padded(src, fill=255):
     """a padded canvas batch [B,C,Hs,Ws] as ragged planes: every sample's whole canvas plane is its image (pitch = Ws)"""
     return pack([s for s in np.asarray(src)], gap=48, fill=fill)
+
+
+def install(monkeypatch):
+    """Swap the four entries the loaders of vitres.data call -- resample_u8, resample_ragged_u8, jpeg_reconstruct_u8 and
+    jpeg_reconstruct_ragged_u8 of vitres.kernels -- for the emulations (torch CPU tensors in and out)."""
+    import torch
+    import vitres.kernels as K
+
+    def padded_resample(src, boxes, out_size, filter, out=None):
+        So_h, So_w = K._out_size(out_size)
+        B, _, Hs, Ws = src.shape
+        if K.resample_band_rows(src.shape[1], Hs, Ws, (So_h, So_w), filter) < 1:     # (raises VR_EUNSUPPORTED as the entry does)
+            raise AssertionError
+        return torch.from_numpy(ER.resample_u8(src.numpy(), boxes.numpy(), So_h, So_w, K._resample_filter(filter)))
+
+    def ragged_resample(src, planes, boxes, C, out_size, filter, out=None, workspace=None, src_bytes=None, bounds=None):
+        So_h, So_w = K._out_size(out_size)
+        assert workspace is not None and bounds is not None
+        return torch.from_numpy(resample_ragged_u8(src.numpy(), planes.numpy(), boxes.numpy(), C, So_h, So_w,
+                                                   K._resample_filter(filter), bounds=bounds, ws_bytes=workspace.numel()))
+
+    def padded_reconstruct(blob, descs, qtabs, Hs, Ws, out=None, workspace=None):
+        out.copy_(torch.from_numpy(EJ.reconstruct_u8(blob.numpy(), descs.numpy(), qtabs.numpy(), Hs, Ws)))
+        return out
+
+    def ragged_reconstruct(blob, descs, qtabs, planes, dst=None, dst_bytes=None, workspace=None, bounds=None):
+        dst.copy_(torch.from_numpy(reconstruct_ragged_u8(blob.numpy(), descs.numpy(), qtabs.numpy(), dst.numpy(), planes.numpy(),
+                                                         bounds=bounds)))
+        return dst
+
+    for name, f in (("resample_u8", padded_resample), ("resample_ragged_u8", ragged_resample),
+                    ("jpeg_reconstruct_u8", padded_reconstruct), ("jpeg_reconstruct_ragged_u8", ragged_reconstruct)):
+        monkeypatch.setattr(K, name, f)

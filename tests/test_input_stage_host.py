@@ -1,6 +1,7 @@
 """The uint8 input side without a GPU: the two entry points' declarations and argument validation (which returns before any
 launch), the normalisation constants, SwitchTokenMix's dtype rules, and DevicePrefetchLoader / ResidentU8Batches with the
-normaliser replaced by tests/emu_input.py."""
+normaliser replaced by tests/emu_input.py; the look-ahead contract for every loader of vitres.data that has it (the crop and JPEG
+loaders on the emulated entries of tests/emu_ragged.py)."""
 import ctypes
 import os
 import re
@@ -10,7 +11,10 @@ import pytest
 import torch
 
 import emu_input
+import emu_jpeg
+import emu_ragged
 from vitres import _lib, data, engine, kernels as K
+from vitres.resized_crop import ResizeCenterCrop
 from vitres.token_mixup import SwitchTokenMix
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,8 +135,35 @@ def u8_set(n, seed=0, shape=(3, 4, 8)):
     return torch.randint(0, 256, (n,) + shape, dtype=torch.uint8, generator=g), torch.arange(n)
 
 
+def look_ahead_cases():
+    """[(name, three host batches of two images under 64 pixels a side, loader -> the look-ahead loader over it)]: every loader of
+    vitres.data that copies one batch ahead, the crop loader on padded and on ragged input, the JPEG loader padded and ragged."""
+    x, y = u8_set(6)
+    rs = np.random.RandomState(1)
+    decoded = [[(rs.randint(0, 256, (h, w, 3)).astype(np.uint8), k) for k, (h, w) in enumerate(sizes)]
+               for sizes in ([(21, 30), (33, 18)], [(40, 25), (19, 44)], [(17, 17), (16, 23)])]
+    names = ["37x53.420.q85", "48x40.444.q30r2", "31x64.422.q95rr", "17x23.gray.q100opt", "fallback.png", "9x17.420.q30r2"]
+    records = emu_jpeg.golden_records(np.load(os.path.join(ROOT, "tests", "golden", "f22_jpeg_pil.npz")))
+    files = [(next(r for r in records if r[0] == n)[2], k % 5) for k, n in enumerate(names)]
+    jpegs = [data.jpeg_collate(files[i:i + 2]) for i in range(0, 6, 2)]
+
+    def crop(loader):
+        return data.DeviceCropLoader(loader, ResizeCenterCrop(16, crop_pct=0.8, interpolation="bilinear"), "cpu")
+    return [("prefetch", [(x[i:i + 2], y[i:i + 2]) for i in range(0, 6, 2)], lambda l: data.DevicePrefetchLoader(l, "cpu", MEAN, STD)),
+            ("crop", [data.pad_collate_u8(b) for b in decoded], crop),
+            ("crop, ragged", [data.ragged_collate_u8(b) for b in decoded], crop),
+            ("jpeg", jpegs, lambda l: data.DeviceJpegLoader(l, "cpu")),
+            ("jpeg, ragged", jpegs, lambda l: data.DeviceJpegLoader(l, "cpu", ragged=True))]
+
+
 def test_device_prefetch_loader(monkeypatch):
     calls = emu_input.install(monkeypatch)
+    emu_ragged.install(monkeypatch)
+    for name, batches, wrap in look_ahead_cases():                # __len__, .sampler and .dataset are the wrapped loader's
+        over = wrap(Loader(batches))
+        assert len(over) == 3 and over.sampler == "the sampler" and over.dataset == "the dataset", name
+        assert len(list(over)) == 3 and len(list(over)) == 3, name                 # re-iterable
+    del calls[:]
     x, y = u8_set(14)
     loader = Loader((x[i:i + 4], y[i:i + 4]) for i in range(0, 14, 4))           # 4, 4, 4, 2
     pre = data.DevicePrefetchLoader(loader, "cpu", MEAN, STD)
@@ -154,18 +185,23 @@ def test_device_prefetch_loader(monkeypatch):
 
 def test_prefetch_runs_one_batch_ahead(monkeypatch):
     emu_input.install(monkeypatch)
-    x, y = u8_set(6)
-    taken = []
+    emu_ragged.install(monkeypatch)
+    for name, batches, wrap in look_ahead_cases():
+        taken = []
 
-    def gen():
-        for i in range(0, 6, 2):
-            taken.append(i)
-            yield x[i:i + 2], y[i:i + 2]
-    it = iter(data.DevicePrefetchLoader(gen(), "cpu", MEAN, STD))
-    next(it)
-    assert taken == [0, 2]                                        # batch 1 was fetched (and its copy issued) before batch 0 was yielded
-    next(it)
-    assert taken == [0, 2, 4]
+        def gen():
+            for i, batch in enumerate(batches):
+                taken.append(i)
+                yield batch
+        it = iter(wrap(gen()))
+        next(it)
+        assert taken == [0, 1], name                              # batch 1 was fetched (and its copy issued) before batch 0 was yielded
+        next(it)
+        assert taken == [0, 1, 2], name
+        next(it)
+        with pytest.raises(StopIteration):
+            next(it)
+        assert taken == [0, 1, 2], name
 
 
 def test_resident_u8_batches(monkeypatch):

@@ -256,33 +256,6 @@ def test_the_padded_plan_still_refuses_the_wide_case():
 
 
 # ---- the loader chains on the emulated entries -------------------------------------------------------------------------------------------
-def _emulate(monkeypatch):
-    def resample_u8(src, boxes, out_size, filter, out=None):
-        So_h, So_w = K._out_size(out_size)
-        B, _, Hs, Ws = src.shape
-        if K.resample_band_rows(src.shape[1], Hs, Ws, (So_h, So_w), filter) < 1:     # (raises VR_EUNSUPPORTED as the entry does)
-            raise AssertionError
-        return torch.from_numpy(ER.resample_u8(src.numpy(), boxes.numpy(), So_h, So_w, K._resample_filter(filter)))
-
-    def resample_ragged_u8(src, planes, boxes, C, out_size, filter, out=None, workspace=None, src_bytes=None, bounds=None):
-        So_h, So_w = K._out_size(out_size)
-        assert workspace is not None and bounds is not None
-        return torch.from_numpy(E.resample_ragged_u8(src.numpy(), planes.numpy(), boxes.numpy(), C, So_h, So_w,
-                                                     K._resample_filter(filter), bounds=bounds, ws_bytes=workspace.numel()))
-
-    def jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=None, workspace=None):
-        out.copy_(torch.from_numpy(EJ.reconstruct_u8(blob.numpy(), descs.numpy(), qtabs.numpy(), Hs, Ws)))
-        return out
-
-    def jpeg_reconstruct_ragged_u8(blob, descs, qtabs, planes, dst=None, dst_bytes=None, workspace=None, bounds=None):
-        dst.copy_(torch.from_numpy(E.reconstruct_ragged_u8(blob.numpy(), descs.numpy(), qtabs.numpy(), dst.numpy(), planes.numpy(),
-                                                           bounds=bounds)))
-        return dst
-
-    for f in (resample_u8, resample_ragged_u8, jpeg_reconstruct_u8, jpeg_reconstruct_ragged_u8):
-        monkeypatch.setattr(K, f.__name__, f)
-
-
 def _transform(kind, S):
     if kind == "train":
         return RandomResizedCrop(S, rng=random.Random(5), generator=torch.Generator().manual_seed(6))
@@ -291,7 +264,7 @@ def _transform(kind, S):
 
 @pytest.mark.parametrize("kind", ["train", "eval"])
 def test_ragged_collate_chain_equals_the_padded_chain_on_the_emulated_entries(kind, monkeypatch):
-    _emulate(monkeypatch)
+    E.install(monkeypatch)
     rs = np.random.RandomState(3)
     batches = [[(rs.randint(0, 256, (h, w, 3)).astype(np.uint8), i % 5) for i, (h, w) in enumerate(sizes)]
                for sizes in ([(21, 30), (33, 18), (17, 17)], [(40, 25), (19, 44), (16, 23)])]
@@ -306,7 +279,7 @@ def test_ragged_collate_chain_equals_the_padded_chain_on_the_emulated_entries(ki
 
 @pytest.mark.parametrize("kind", ["train", "eval"])
 def test_ragged_jpeg_chain_equals_the_padded_chain_on_the_emulated_entries(kind, monkeypatch):
-    _emulate(monkeypatch)
+    E.install(monkeypatch)
     names = ["37x53.420.q85", "48x40.444.q30r2", "31x64.422.q95rr", "17x23.gray.q100opt", "fallback.png", "9x17.420.q30r2"]
     records = [next(r for r in EJ.golden_records(F22) if r[0] == n) for n in names]
     files = [(r[2], k % 5) for k, r in enumerate(records)]
@@ -323,7 +296,7 @@ def test_ragged_jpeg_chain_equals_the_padded_chain_on_the_emulated_entries(kind,
 
 
 def test_big_images_go_through_the_ragged_chain_where_the_padded_chain_is_refused(monkeypatch):
-    _emulate(monkeypatch)
+    E.install(monkeypatch)
     collated, pixels, boxes, size, filt, crops = _collate_big()
 
     S = size[0]

@@ -353,7 +353,10 @@ def test_eager_epoch_on_uint8_with_erase_equals_normalise_erase_mix(monkeypatch,
     calls = emu_erase.install(monkeypatch)
     norm = K.norm_constants(MEAN, STD)
     runs = []
-    for fused in (True, False):
+    # fused: the uint8 batches through the erase wrapper; staged: the three stages written out, mixed by the reference; and for the
+    # token mix a third run, the staged batches through SwitchTokenMix's own un-erased path (kernels.token_mix, emulated by name)
+    for variant in ("fused", "staged") + (("by_name",) if kind == "token_mix" else ()):
+        fused = variant == "fused"
         er = new_erase(mode)
         if fused:
             kw = dict(input_norm=(MEAN, STD), erase=er)
@@ -370,7 +373,7 @@ def test_eager_epoch_on_uint8_with_erase_equals_normalise_erase_mix(monkeypatch,
             how = dict(mixup_fn=mix)
         else:
             mix = SwitchTokenMix(1, num_classes=recipe.MICRO_CLASSES, **kw)
-            how = dict(patch_mixup_fn=mix if fused else RefTokenMix(mix))
+            how = dict(patch_mixup_fn=RefTokenMix(mix) if variant == "staged" else mix)
         m = micro()
         opt = torch.optim.AdamW(engine.param_groups_weight_decay(m, 0.05), lr=1e-3)
         crit = Crit()
@@ -380,7 +383,11 @@ def test_eager_epoch_on_uint8_with_erase_equals_normalise_erase_mix(monkeypatch,
         stats = engine.train_one_epoch(m, crit, loader, opt, "cpu", 31, None, max_norm=None, print_freq=0, arch_sample="multi",
                                        logger=Quiet, **how)
         runs.append((stats, crit.seen, m.state_dict(), np.random.get_state(), calls[before:], loader))
-    (sa, la, pa, ga, ca, _), (sb, lb, pb, gb, cb, staged) = runs
+    (sa, la, pa, ga, ca, _), (sb, lb, pb, gb, cb, staged) = runs[:2]
+    for sc, lc, pc, gc, cc, _ in runs[2:]:                        # the un-erased mix by name IS the reference mix
+        assert [(c["what"], c["erase"]) for c in cc] == [("token_mix", None)] * 3
+        assert lc == lb and sc == sb and all(torch.equal(pc[k], pb[k]) for k in pb)
+        assert gc[0] == gb[0] and np.array_equal(gc[1], gb[1]) and gc[2:] == gb[2:]
     assert len(ca) == 3 and not cb                                # the fused run went through the erase wrapper, once per batch
     want = "mixup_u8_erase" if kind == "mixup" else "token_mix_u8_erase"
     any_erased = False

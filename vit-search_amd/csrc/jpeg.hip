@@ -293,6 +293,33 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_place_ragged_kernel(const uin
     }
 }
 
+// What both entries check, in the order EINVAL, EUNSUPPORTED, EALIGN.  dst: the canvas (dst_mask 3) or the flat buffer (15); `more`:
+// whether the entry's own further arguments are given (the ragged one's planes and dst_bytes), refused with the first EINVALs.
+int jp_check(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs, const uint16_t* qtabs, const uint8_t* dst,
+             uintptr_t dst_mask, bool more, int32_t B, int32_t Hs, int32_t Ws, const void* workspace, size_t ws_bytes) {
+    if (!blob || !descs || !qtabs || !dst || !more || blob_bytes <= 0 || B <= 0 || Hs <= 0 || Ws <= 0) return VR_EINVAL;
+    if (!workspace || ws_bytes < vr_jpeg_ws_bytes(blob_bytes) || workspace == blob || workspace == (const void*)dst
+        || (const void*)dst == blob)
+        return VR_EINVAL;
+    if (Ws % 4 || B > 65535 || Hs > JP_MAX_SIDE || Ws > JP_MAX_SIDE) return VR_EUNSUPPORTED;
+    if (((uintptr_t)blob & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)dst & dst_mask) || ((uintptr_t)descs & 3)
+        || ((uintptr_t)qtabs & 1))
+        return VR_EALIGN;
+    return VR_OK;
+}
+
+// launch 1 of both entries: the component sample planes into the workspace
+int jp_launch_idct(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs, const uint16_t* qtabs, int32_t B, int32_t Hs,
+                   int32_t Ws, void* workspace, vr_stream_t stream) {
+    // an image inside the bounds has at most this many blocks (4:4:4: three planes of whole MCUs); the kernel strides over more
+    const long long most = 3LL * (Ws / 8 + 2) * (Hs / 8 + 2);
+    const unsigned gx = (unsigned)((most + JP_THREADS - 1) / JP_THREADS);
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(gx, B), dim3(JP_THREADS), 0, (hipStream_t)stream, (const uint8_t*)blob,
+                       (long long)blob_bytes, descs, qtabs, (uint8_t*)workspace, Hs, Ws);
+    VR_CHECK_LAUNCH();
+    return VR_OK;
+}
+
 }  // namespace
 
 static_assert(sizeof(vr_jpeg_desc) == 64, "vr_jpeg_desc is 64 bytes: the host marshals the table as 16 int32 per record");
@@ -305,20 +332,9 @@ extern "C" size_t vr_jpeg_ws_bytes(int64_t blob_bytes) {
 extern "C" int vr_jpeg_reconstruct_u8(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs, const uint16_t* qtabs,
                                       uint8_t* canvas, int32_t B, int32_t Hs, int32_t Ws, void* workspace, size_t ws_bytes,
                                       vr_stream_t stream) {
-    if (!blob || !descs || !qtabs || !canvas || blob_bytes <= 0 || B <= 0 || Hs <= 0 || Ws <= 0) return VR_EINVAL;
-    if (!workspace || ws_bytes < vr_jpeg_ws_bytes(blob_bytes) || workspace == blob || workspace == (void*)canvas
-        || (const void*)canvas == blob)
-        return VR_EINVAL;
-    if (Ws % 4 || B > 65535 || Hs > JP_MAX_SIDE || Ws > JP_MAX_SIDE) return VR_EUNSUPPORTED;
-    if (((uintptr_t)blob & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)canvas & 3) || ((uintptr_t)descs & 3)
-        || ((uintptr_t)qtabs & 1))
-        return VR_EALIGN;
-    // an image inside the canvas has at most this many blocks (4:4:4: three planes of whole MCUs); the kernel strides over more
-    const long long most = 3LL * (Ws / 8 + 2) * (Hs / 8 + 2);
-    const unsigned gx = (unsigned)((most + JP_THREADS - 1) / JP_THREADS);
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(gx, B), dim3(JP_THREADS), 0, (hipStream_t)stream, (const uint8_t*)blob,
-                       (long long)blob_bytes, descs, qtabs, (uint8_t*)workspace, Hs, Ws);
-    VR_CHECK_LAUNCH();
+    int rc = jp_check(blob, blob_bytes, descs, qtabs, canvas, 3, true, B, Hs, Ws, workspace, ws_bytes);
+    if (rc == VR_OK) rc = jp_launch_idct(blob, blob_bytes, descs, qtabs, B, Hs, Ws, workspace, stream);
+    if (rc != VR_OK) return rc;
     const long long quads = (long long)Hs * (Ws / 4);
     hipLaunchKernelGGL(jpeg_place_kernel, dim3((unsigned)((quads + JP_THREADS - 1) / JP_THREADS), B), dim3(JP_THREADS), 0,
                        (hipStream_t)stream, (const uint8_t*)blob, (long long)blob_bytes, descs, (const uint8_t*)workspace, canvas, Hs,
@@ -330,19 +346,10 @@ extern "C" int vr_jpeg_reconstruct_u8(const void* blob, int64_t blob_bytes, cons
 extern "C" int vr_jpeg_reconstruct_ragged_u8(const void* blob, int64_t blob_bytes, const vr_jpeg_desc* descs, const uint16_t* qtabs,
                                              uint8_t* dst, int64_t dst_bytes, const vr_ragged_plane* planes, int32_t B, int32_t Hs,
                                              int32_t Ws, void* workspace, size_t ws_bytes, vr_stream_t stream) {
-    if (!blob || !descs || !qtabs || !dst || !planes || blob_bytes <= 0 || dst_bytes <= 0 || B <= 0 || Hs <= 0 || Ws <= 0)
-        return VR_EINVAL;
-    if (!workspace || ws_bytes < vr_jpeg_ws_bytes(blob_bytes) || workspace == blob || workspace == (void*)dst || (const void*)dst == blob)
-        return VR_EINVAL;
-    if (Ws % 4 || B > 65535 || Hs > JP_MAX_SIDE || Ws > JP_MAX_SIDE) return VR_EUNSUPPORTED;
-    if (((uintptr_t)blob & 15) || ((uintptr_t)workspace & 15) || ((uintptr_t)dst & 15) || ((uintptr_t)planes & 7)
-        || ((uintptr_t)descs & 3) || ((uintptr_t)qtabs & 1))
-        return VR_EALIGN;
-    const long long most = 3LL * (Ws / 8 + 2) * (Hs / 8 + 2);                        // as the padded entry: Hs, Ws bound every image
-    const unsigned gx = (unsigned)((most + JP_THREADS - 1) / JP_THREADS);
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3(gx, B), dim3(JP_THREADS), 0, (hipStream_t)stream, (const uint8_t*)blob,
-                       (long long)blob_bytes, descs, qtabs, (uint8_t*)workspace, Hs, Ws);
-    VR_CHECK_LAUNCH();
+    int rc = jp_check(blob, blob_bytes, descs, qtabs, dst, 15, planes && dst_bytes > 0, B, Hs, Ws, workspace, ws_bytes);
+    if (rc == VR_OK && ((uintptr_t)planes & 7)) rc = VR_EALIGN;
+    if (rc == VR_OK) rc = jp_launch_idct(blob, blob_bytes, descs, qtabs, B, Hs, Ws, workspace, stream);
+    if (rc != VR_OK) return rc;
     const long long per = (long long)JP_THREADS * JP_RAGGED_QUADS, quads = (long long)Hs * (Ws / 4);
     hipLaunchKernelGGL(jpeg_place_ragged_kernel, dim3((unsigned)((quads + per - 1) / per), B), dim3(JP_THREADS), 0, (hipStream_t)stream,
                        (const uint8_t*)blob, (long long)blob_bytes, descs, (const uint8_t*)workspace, dst, (long long)dst_bytes, planes,

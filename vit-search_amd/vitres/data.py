@@ -39,21 +39,52 @@ from . import jpeg as J
 from . import kernels as K
 
 
-class DevicePrefetchLoader:
-    """Counterpart of timm's PrefetchLoader over a loader of (uint8 NCHW CPU batch, target) pairs: the next batch is copied to
-    `device` on a side stream while the current one is consumed, and every batch is yielded as (normalize_u8(batch), target) on the
-    current stream.  normalize=False yields the uint8 device batch itself -- the training loop's form, where
-    SwitchTokenMix(input_norm=(mean, std)) normalises inside the mix.  mean / std: per-channel, 0..1 units.  Pinned host batches
-    (pin_memory=True) make the copies asynchronous.  erase=RandomErasing(...): every batch is yielded erased as well
-    (vr_normalize_u8_erase, the same pass); with normalize=False the mix owns the erase and erase= here raises.  __len__, .sampler
-    and .dataset are the wrapped loader's."""
+class _Upload:
+    """The copies of one batch: every tensor a loader sends to the device goes through here, so what has to be kept alive across
+    the two streams is known here and nowhere else.  With a side stream the copies are non-blocking and issued on it (pinned host
+    batches make them asynchronous), int tables are staged in pinned memory, and hand_over() makes the current stream wait for them
+    and own the tensors.  side=None (not a GPU): plain copies, nothing to overlap or to wait for."""
 
-    def __init__(self, loader, device, mean=K.IMAGENET_DEFAULT_MEAN, std=K.IMAGENET_DEFAULT_STD, normalize=True, erase=None):
-        if erase is not None and not normalize:
-            raise ValueError("DevicePrefetchLoader(normalize=False, erase=...): random erasing works on normalised pixels, so it "
-                             "belongs to whoever normalises -- pass erase= to SwitchTokenMix / Mixup(input_norm=...) instead")
-        self.loader, self.device, self.normalize, self.erase = loader, torch.device(device), normalize, erase
-        self.norm = K.norm_constants(mean, std)
+    def __init__(self, device, side):
+        self.device, self.side, self.moved, self.copied = device, side, [], None
+
+    def __call__(self, t):
+        if t.is_cuda:                             # (a RaggedCanvas's buffer, made on the consumer's stream: nothing to copy or to keep)
+            return t
+        if self.side is None:
+            return t.to(self.device)
+        with torch.cuda.stream(self.side):
+            t = t.to(self.device, non_blocking=True)
+        self.moved.append(t)
+        return t
+
+    def table(self, array):
+        """A host int array as an int32 device tensor."""
+        host = torch.empty(array.shape, dtype=torch.int32, pin_memory=self.side is not None)
+        host.numpy()[...] = array
+        return self(host)
+
+    def issued(self):
+        self.copied = None if self.side is None else self.side.record_event()
+
+    def hand_over(self):
+        if self.copied is not None:
+            cur = torch.cuda.current_stream(self.device)
+            cur.wait_event(self.copied)
+            for t in self.moved:                  # (allocated on the side stream, used on this one)
+                t.record_stream(cur)
+
+
+class _LookAheadLoader:
+    """timm's PrefetchLoader pattern, once: while a batch is consumed the next one is fetched from the wrapped loader, staged and
+    copied to `device` on a side stream; every batch is handed over on the current stream.  A subclass says what a batch needs:
+      _stage(up, *batch)   at upload time, in the loader's order: the host checks, the random draws, and up(tensor) / up.table(array)
+                           for whatever goes to the device; returns the arguments of _launch
+      _launch(*staged)     at hand-over, on the current stream, after the copies: the kernels; returns what is yielded
+    __len__, .sampler and .dataset are the wrapped loader's."""
+
+    def __init__(self, loader, device):
+        self.loader, self.device = loader, torch.device(device)
 
     def __len__(self):
         return len(self.loader)
@@ -66,31 +97,51 @@ class DevicePrefetchLoader:
     def dataset(self):
         return self.loader.dataset
 
-    def _upload(self, side, batch, target):
-        if batch.dtype != torch.uint8:
-            raise TypeError("DevicePrefetchLoader takes uint8 NCHW batches (timm's fast_collate), got %s" % batch.dtype)
-        if side is None:                      # (not a GPU: nothing to overlap; the normaliser itself has no CPU form)
-            return batch.to(self.device), target.to(self.device), None
-        with torch.cuda.stream(side):
-            return batch.to(self.device, non_blocking=True), target.to(self.device, non_blocking=True), side.record_event()
+    def _upload(self, side, batch):
+        up = _Upload(self.device, side)
+        staged = self._stage(up, *batch)
+        up.issued()
+        return up, staged
+
+    def _hand_over(self, up, staged):
+        up.hand_over()
+        return self._launch(*staged)
 
     def __iter__(self):
         side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         ahead = None
-        for batch, target in self.loader:
-            nxt = self._upload(side, batch, target)
+        for batch in self.loader:
+            nxt = self._upload(side, batch)
             if ahead is not None:
                 yield self._hand_over(*ahead)
             ahead = nxt
         if ahead is not None:
             yield self._hand_over(*ahead)
 
-    def _hand_over(self, u8, target, copied):
-        if copied is not None:
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(copied)
-            u8.record_stream(cur)             # (allocated on the side stream, used on this one)
-            target.record_stream(cur)
+
+class DevicePrefetchLoader(_LookAheadLoader):
+    """Counterpart of timm's PrefetchLoader over a loader of (uint8 NCHW CPU batch, target) pairs: the next batch is copied to
+    `device` on a side stream while the current one is consumed, and every batch is yielded as (normalize_u8(batch), target) on the
+    current stream.  normalize=False yields the uint8 device batch itself -- the training loop's form, where
+    SwitchTokenMix(input_norm=(mean, std)) normalises inside the mix.  mean / std: per-channel, 0..1 units.  Pinned host batches
+    (pin_memory=True) make the copies asynchronous.  erase=RandomErasing(...): every batch is yielded erased as well
+    (vr_normalize_u8_erase, the same pass); with normalize=False the mix owns the erase and erase= here raises.  __len__, .sampler
+    and .dataset are the wrapped loader's."""
+
+    def __init__(self, loader, device, mean=K.IMAGENET_DEFAULT_MEAN, std=K.IMAGENET_DEFAULT_STD, normalize=True, erase=None):
+        if erase is not None and not normalize:
+            raise ValueError("DevicePrefetchLoader(normalize=False, erase=...): random erasing works on normalised pixels, so it "
+                             "belongs to whoever normalises -- pass erase= to SwitchTokenMix / Mixup(input_norm=...) instead")
+        super().__init__(loader, device)
+        self.normalize, self.erase = normalize, erase
+        self.norm = K.norm_constants(mean, std)
+
+    def _stage(self, up, batch, target):
+        if batch.dtype != torch.uint8:
+            raise TypeError("DevicePrefetchLoader takes uint8 NCHW batches (timm's fast_collate), got %s" % batch.dtype)
+        return up(batch), up(target)
+
+    def _launch(self, u8, target):
         if self.erase is not None:
             B, _, H, W = u8.shape
             return K.normalize_u8_erase(u8, *self.norm, self.erase.next_args(B, H, W, u8.device if u8.is_cuda else None)), target
@@ -127,23 +178,34 @@ class ResidentU8Batches:
             yield K.normalize_u8(u8, *self.norm, out=out), self.targets[lo:lo + self.batch_size]
 
 
+def _sample_labels(samples, what):
+    """The labels of a non-empty list of (image, label) samples as an int64 tensor."""
+    if not samples:
+        raise ValueError("%s: an empty batch" % what)
+    return torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
+
+
+def _decoded_samples(samples, what):
+    """(images, sizes int32 [B,2] of (h, w), labels int64 [B]) of a list of (HWC uint8 array, label): non-empty arrays of one channel
+    count, or TypeError."""
+    labels = _sample_labels(samples, what)
+    images = [np.asarray(img) for img, _ in samples]
+    for img in images:
+        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != images[0].shape[2] or 0 in img.shape:
+            raise TypeError("%s takes non-empty HWC uint8 arrays of one channel count, got %s %s" % (what, img.dtype, img.shape))
+    return images, np.array([img.shape[:2] for img in images], dtype=np.int32), labels
+
+
 def pad_collate_u8(samples):
     """Collate a list of (HWC uint8 array, label) -- decoded images of any sizes, one channel count -- into
     (canvas uint8 [B,C,Hs,Ws], sizes int32 [B,2] of (h, w), labels int64 [B]): every image sits in the top-left corner of its
     canvas plane, the rest is zero; Hs and Ws are the batch maxima rounded up to a multiple of 4 (vr_resample_u8 reads rows as
     dwords).  What a DataLoader(collate_fn=pad_collate_u8) hands to DeviceCropLoader."""
-    if not samples:
-        raise ValueError("pad_collate_u8: an empty batch")
-    images = [np.asarray(img) for img, _ in samples]
-    for img in images:
-        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != images[0].shape[2] or 0 in img.shape:
-            raise TypeError("pad_collate_u8 takes non-empty HWC uint8 arrays of one channel count, got %s %s" % (img.dtype, img.shape))
-    sizes = np.array([img.shape[:2] for img in images], dtype=np.int32)
+    images, sizes, labels = _decoded_samples(samples, "pad_collate_u8")
     Hs, Ws = ((int(v) + 3) // 4 * 4 for v in sizes.max(axis=0))
     canvas = np.zeros((len(images), images[0].shape[2], Hs, Ws), dtype=np.uint8)
     for b, img in enumerate(images):
         canvas[b, :, :img.shape[0], :img.shape[1]] = img.transpose(2, 0, 1)
-    labels = torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
     return torch.from_numpy(canvas), torch.from_numpy(sizes), labels
 
 
@@ -153,14 +215,8 @@ def ragged_collate_u8(samples):
     works.  Every image lies in C planes of its own size (kernels.ragged_layout: pitch = its width rounded up to 4, rows = its
     height, channel c at off + c * rows * pitch, every sample on a multiple of 16 bytes); pad columns and the bytes between
     samples are zero.  The first reserved word of every record notes the channel count (the device ignores it).  What a DataLoader(collate_fn=ragged_collate_u8) hands to DeviceCropLoader."""
-    if not samples:
-        raise ValueError("ragged_collate_u8: an empty batch")
-    images = [np.asarray(img) for img, _ in samples]
-    for img in images:
-        if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != images[0].shape[2] or 0 in img.shape:
-            raise TypeError("ragged_collate_u8 takes non-empty HWC uint8 arrays of one channel count, got %s %s" % (img.dtype, img.shape))
+    images, sizes, labels = _decoded_samples(samples, "ragged_collate_u8")
     C = images[0].shape[2]
-    sizes = np.array([img.shape[:2] for img in images], dtype=np.int32)
     planes, nbytes = K.ragged_layout(sizes, C)
     planes["reserved"][:, 0] = C              # (for DeviceCropLoader: the device ignores the reserved words)
     flat = np.zeros(nbytes, dtype=np.uint8)
@@ -168,7 +224,6 @@ def ragged_collate_u8(samples):
         h, w = img.shape[:2]
         off, pitch = int(p["off"]), int(p["pitch"])
         flat[off:off + C * h * pitch].reshape(C, h, pitch)[:, :, :w] = img.transpose(2, 0, 1)
-    labels = torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
     return (torch.from_numpy(flat), torch.from_numpy(planes.view(np.int32).reshape(len(images), K.RAGGED_PLANE_INTS)),
             torch.from_numpy(sizes), labels)
 
@@ -189,7 +244,7 @@ class RaggedCanvas:
         return view if size is None else view[:, :int(size[0]), :int(size[1])]
 
 
-class DeviceCropLoader:
+class DeviceCropLoader(_LookAheadLoader):
     """Over a loader of (canvas uint8 [B,C,Hs,Ws], sizes [B,2], labels) host batches (pad_collate_u8): yields
     (uint8 [B,C,S,S] on `device`, labels on `device`), the canvas cropped, resized and mirrored by vr_resample_u8 with the boxes
     `transform.draw(sizes)` makes (a vitres.resized_crop.RandomResizedCrop or ResizeCenterCrop: .draw, .size, .filter).  The canvas,
@@ -205,25 +260,18 @@ class DeviceCropLoader:
     __len__, .sampler and .dataset are the wrapped loader's."""
 
     def __init__(self, loader, transform, device, augment=None):
-        self.loader, self.transform, self.device, self.augment = loader, transform, torch.device(device), augment
+        super().__init__(loader, device)
+        self.transform, self.augment = transform, augment
         self._rws = None                      # the ragged resample's workspace
         if augment is not None:
             size = (transform.size, transform.size) if isinstance(transform.size, int) else tuple(transform.size)
             if tuple(augment.size) != size:
                 raise ValueError("DeviceCropLoader: the augmentation draws for %s images, the transform makes %s" % (augment.size, size))
 
-    def __len__(self):
-        return len(self.loader)
-
-    @property
-    def sampler(self):
-        return self.loader.sampler
-
-    @property
-    def dataset(self):
-        return self.loader.dataset
-
-    def _upload(self, side, canvas, sizes, labels):
+    def _stage(self, up, *batch):
+        if len(batch) == 4 or isinstance(batch[0], RaggedCanvas):
+            return self._stage_ragged(up, *batch)
+        canvas, sizes, labels = batch
         if canvas.dtype != torch.uint8 or canvas.dim() != 4:
             raise TypeError("DeviceCropLoader takes uint8 [B,C,Hs,Ws] canvases (pad_collate_u8), got %s %s" % (canvas.dtype,
                                                                                                               tuple(canvas.shape)))
@@ -231,37 +279,11 @@ class DeviceCropLoader:
         sizes = np.asarray(sizes, dtype=np.int64)
         if sizes.shape != (B, 2) or (sizes[:, 0] > Hs).any() or (sizes[:, 1] > Ws).any():
             raise ValueError("DeviceCropLoader: sizes must hold one (h, w) inside the %d x %d canvas per sample" % (Hs, Ws))
-        table = K.check_resample_boxes(self.transform.draw(sizes), B, Hs, Ws, self.transform.size)
-        host = torch.empty(table.shape, dtype=torch.int32, pin_memory=side is not None)
-        host.numpy()[...] = table
-        ops = None
-        if self.augment is not None:
-            ra = K.check_ra_table(self.augment.draw(B), B)
-            ops = torch.empty(ra.shape, dtype=torch.int32, pin_memory=side is not None)
-            ops.numpy()[...] = ra
-        if side is None:                      # (not a GPU: nothing to overlap; the kernel itself has no CPU form)
-            return (canvas.to(self.device), host.to(self.device), labels.to(self.device), None,
-                    None if ops is None else ops.to(self.device))
-        with torch.cuda.stream(side):
-            canvas, host, labels = (t.to(self.device, non_blocking=True) for t in (canvas, host, labels))
-            ops = None if ops is None else ops.to(self.device, non_blocking=True)
-            return canvas, host, labels, side.record_event(), ops
+        _, table, ops = self._draw(up, sizes, lambda boxes: K.check_resample_boxes(boxes, B, Hs, Ws, self.transform.size))
+        canvas = up(canvas)
+        return (lambda: K.resample_u8(canvas, table, self.transform.size, self.transform.filter)), ops, up(labels)
 
-    def __iter__(self):
-        side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
-        ahead = None
-        for batch in self.loader:
-            if len(batch) == 4 or isinstance(batch[0], RaggedCanvas):
-                nxt = (self._hand_over_ragged, self._upload_ragged(side, *batch))
-            else:
-                nxt = (self._hand_over, self._upload(side, *batch))
-            if ahead is not None:
-                yield ahead[0](*ahead[1])
-            ahead = nxt
-        if ahead is not None:
-            yield ahead[0](*ahead[1])
-
-    def _upload_ragged(self, side, flat, planes, sizes, labels=None):
+    def _stage_ragged(self, up, flat, planes, sizes, labels=None):
         if isinstance(flat, RaggedCanvas):    # (already on the device: DeviceJpegLoader(ragged=True) yields (canvas, sizes, labels))
             flat, planes, sizes, labels, C = flat.flat, flat.host_planes.copy(), planes, sizes, flat.channels
         else:
@@ -270,57 +292,31 @@ class DeviceCropLoader:
                                 "(ragged_collate_u8)")
             planes = np.ascontiguousarray(planes.numpy()).view(K.RAGGED_PLANE_DTYPE).reshape(-1).copy()
             C = int(planes["reserved"][0, 0]) or 3   # (ragged_collate_u8's note of the channel count: a flat buffer does not say)
-        B = planes.shape[0]
         sizes = np.asarray(sizes, dtype=np.int64)
         K.check_ragged_planes(planes, C, int(flat.numel()), sizes, "DeviceCropLoader")
         size = self.transform.size
-        table = K.check_ragged_boxes(self.transform.draw(sizes), planes, size)
-        So_w = size if isinstance(size, int) else size[1]
-        need = K.ragged_ws_offsets(planes, C, So_w, table[:, 3])
+        boxes, table, ops = self._draw(up, sizes, lambda boxes: K.check_ragged_boxes(boxes, planes, size))
+        need = K.ragged_ws_offsets(planes, C, K._out_size(size)[1], boxes[:, 3])     # (fills the planes' ws_off: before they are staged)
         bounds = K.ragged_bounds(planes)
-        pinned = side is not None
-        host = torch.empty(table.shape, dtype=torch.int32, pin_memory=pinned)
-        host.numpy()[...] = table
-        hplanes = torch.empty((B, K.RAGGED_PLANE_INTS), dtype=torch.int32, pin_memory=pinned)
-        hplanes.numpy()[...] = planes.view(np.int32).reshape(B, K.RAGGED_PLANE_INTS)
-        ops = None
-        if self.augment is not None:
-            ra = K.check_ra_table(self.augment.draw(B), B)
-            ops = torch.empty(ra.shape, dtype=torch.int32, pin_memory=pinned)
-            ops.numpy()[...] = ra
-        if side is None:
-            return (flat.to(self.device), hplanes.to(self.device), host.to(self.device), labels.to(self.device), C, need, bounds, None,
-                    None if ops is None else ops.to(self.device))
-        with torch.cuda.stream(side):
-            moved = flat if flat.is_cuda else flat.to(self.device, non_blocking=True)
-            hplanes, host, labels = (t.to(self.device, non_blocking=True) for t in (hplanes, host, labels))
-            ops = None if ops is None else ops.to(self.device, non_blocking=True)
-            return moved, hplanes, host, labels, C, need, bounds, side.record_event(), ops
+        flat, planes = up(flat), up.table(planes.view(np.int32).reshape(-1, K.RAGGED_PLANE_INTS))
 
-    def _hand_over_ragged(self, flat, planes, table, labels, C, need, bounds, copied, ops=None):
-        if copied is not None:
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(copied)
-            for t in (flat, planes, table, labels) + (() if ops is None else (ops,)):
-                t.record_stream(cur)
-        if self._rws is None or self._rws.numel() < need:
-            self._rws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        crop = K.resample_ragged_u8(flat, planes, table, C, self.transform.size, self.transform.filter, workspace=self._rws,
-                                    bounds=bounds)
-        if ops is None:
-            return crop, labels
-        return K.rand_augment_u8(crop, ops, self.augment.fill), labels
+        def resample():
+            if self._rws is None or self._rws.numel() < need:
+                self._rws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            return K.resample_ragged_u8(flat, planes, table, C, size, self.transform.filter, workspace=self._rws, bounds=bounds)
+        return resample, ops, up(labels)
 
-    def _hand_over(self, canvas, table, labels, copied, ops=None):
-        if copied is not None:
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(copied)
-            for t in (canvas, table, labels) + (() if ops is None else (ops,)):  # (allocated on the side stream, used on this one)
-                t.record_stream(cur)
-        crop = K.resample_u8(canvas, table, self.transform.size, self.transform.filter)
-        if ops is None:
-            return crop, labels
-        return K.rand_augment_u8(crop, ops, self.augment.fill), labels
+    def _draw(self, up, sizes, check):
+        """A batch's random draws, in their order -- the boxes, then the RandAugment table -- each checked on the host and staged:
+        (the checked host box table, the device one, the device op table or None)."""
+        boxes = check(self.transform.draw(sizes))
+        table = up.table(boxes)
+        ops = None if self.augment is None else up.table(K.check_ra_table(self.augment.draw(len(sizes)), len(sizes)))
+        return boxes, table, ops
+
+    def _launch(self, resample, ops, labels):
+        crop = resample()
+        return (crop if ops is None else K.rand_augment_u8(crop, ops, self.augment.fill)), labels
 
 
 def _pil_rgb(data):
@@ -336,8 +332,7 @@ def jpeg_collate(samples):
     Every other file, and every stream whose entropy decode fails, is decoded by PIL's Image.open(...).convert('RGB') and stored as
     planar pixels (kind 1): the fallback is PIL's result by construction, PIL's exception for a file it cannot read included.  Every
     image starts on a multiple of 128 bytes, every component on a multiple of its block size (128 bytes, 64 for pixels)."""
-    if not samples:
-        raise ValueError("jpeg_collate: an empty batch")
+    labels = _sample_labels(samples, "jpeg_collate")
     B = len(samples)
     files = [data if isinstance(data, (bytes, np.ndarray)) else bytes(data) for data, _ in samples]
     infos, raws, slots, total = [], [], [], 0
@@ -382,12 +377,11 @@ def jpeg_collate(samples):
             for c in range(3):
                 d["off"][c], d["bw"][c], d["bh"][c] = (lo + c * 64 * bh * bw) // K.JPEG_OFF_UNIT, bw, bh
         sizes[b] = d["height"], d["width"]
-    labels = torch.as_tensor(np.asarray([int(label) for _, label in samples], dtype=np.int64))
     return (torch.from_numpy(blob), torch.from_numpy(descs.view(np.int32).reshape(B, K.JPEG_DESC_INTS)),
             torch.from_numpy(qtabs.view(np.int16)), torch.from_numpy(sizes), labels)
 
 
-class DeviceJpegLoader:
+class DeviceJpegLoader(_LookAheadLoader):
     """Over a loader of jpeg_collate batches (DataLoader(..., collate_fn=jpeg_collate, pin_memory=True)): yields
     (canvas uint8 [B,3,Hs,Ws] on `device`, sizes [B,2] on the host, labels), the triple DeviceCropLoader takes from a pad_collate_u8
     loader -- the same bytes, made on the device by vr_jpeg_reconstruct_u8 from the coefficients the workers decoded.  Hs, Ws are the
@@ -401,21 +395,11 @@ class DeviceJpegLoader:
     __len__, .sampler and .dataset are the wrapped loader's."""
 
     def __init__(self, loader, device, ragged=False):
-        self.loader, self.device, self.ragged = loader, torch.device(device), bool(ragged)
+        super().__init__(loader, device)
+        self.ragged = bool(ragged)
         self._canvas, self._ws, self._turn = [None, None], None, 0
 
-    def __len__(self):
-        return len(self.loader)
-
-    @property
-    def sampler(self):
-        return self.loader.sampler
-
-    @property
-    def dataset(self):
-        return self.loader.dataset
-
-    def _upload(self, side, blob, descs, qtabs, sizes, labels):
+    def _stage(self, up, blob, descs, qtabs, sizes, labels):
         if blob.dtype != torch.uint8 or blob.dim() != 1 or descs.dtype != torch.int32 or descs.dim() != 2:
             raise TypeError("DeviceJpegLoader takes jpeg_collate batches (blob uint8 [n], descs int32 [B,16], ...)")
         Hs, Ws = ((int(v) + 3) // 4 * 4 for v in np.asarray(sizes).max(axis=0))
@@ -423,52 +407,23 @@ class DeviceJpegLoader:
         planes = None
         if self.ragged:
             layout, nbytes = K.ragged_layout(np.asarray(sizes), 3)
-            table = K.check_ragged_planes(layout, 3, nbytes, np.asarray(sizes), "DeviceJpegLoader")
-            dev_table = torch.empty(table.shape, dtype=torch.int32, pin_memory=side is not None)
-            dev_table.numpy()[...] = table
-            planes = (layout, nbytes, dev_table)
-        if side is None:                      # (not a GPU: nothing to overlap; the kernel itself has no CPU form)
-            if planes is not None:
-                planes = planes[:2] + (planes[2].to(self.device),)
-            return blob.to(self.device), descs.to(self.device), qtabs.to(self.device), sizes, labels, Hs, Ws, None, planes
-        with torch.cuda.stream(side):
-            blob, descs, qtabs = (t.to(self.device, non_blocking=True) for t in (blob, descs, qtabs))
-            if planes is not None:
-                planes = planes[:2] + (planes[2].to(self.device, non_blocking=True),)
-            return blob, descs, qtabs, sizes, labels, Hs, Ws, side.record_event(), planes
-
-    def __iter__(self):
-        side = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
-        ahead = None
-        for batch in self.loader:
-            nxt = self._upload(side, *batch)
-            if ahead is not None:
-                yield self._hand_over(*ahead)
-            ahead = nxt
-        if ahead is not None:
-            yield self._hand_over(*ahead)
+            planes = (layout, nbytes, up.table(K.check_ragged_planes(layout, 3, nbytes, np.asarray(sizes), "DeviceJpegLoader")))
+        return up(blob), up(descs), up(qtabs), sizes, labels, Hs, Ws, planes
 
     def _buffer(self, held, nbytes):
         if held is None or held.numel() < nbytes:
             held = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return held
 
-    def _hand_over(self, blob, descs, qtabs, sizes, labels, Hs, Ws, copied, planes=None):
-        if copied is not None:
-            cur = torch.cuda.current_stream(self.device)
-            cur.wait_event(copied)
-            for t in (blob, descs, qtabs) + (() if planes is None else (planes[2],)):  # (allocated on the side stream, used on this one)
-                t.record_stream(cur)
+    def _launch(self, blob, descs, qtabs, sizes, labels, Hs, Ws, planes):
         B = int(descs.shape[0])
         turn, self._turn = self._turn, self._turn ^ 1
-        if planes is not None:
-            layout, nbytes, table = planes
-            self._canvas[turn] = self._buffer(self._canvas[turn], nbytes)
-            self._ws = self._buffer(self._ws, K.jpeg_ws_bytes(blob.numel()))
-            flat = self._canvas[turn][:nbytes]
-            K.jpeg_reconstruct_ragged_u8(blob, descs, qtabs, table, dst=flat, workspace=self._ws, bounds=K.ragged_bounds(layout))
-            return RaggedCanvas(flat, table, layout, 3), sizes, labels
-        self._canvas[turn] = self._buffer(self._canvas[turn], B * 3 * Hs * Ws)
+        nbytes = B * 3 * Hs * Ws if planes is None else planes[1]
+        self._canvas[turn] = self._buffer(self._canvas[turn], nbytes)
         self._ws = self._buffer(self._ws, K.jpeg_ws_bytes(blob.numel()))
-        canvas = self._canvas[turn][:B * 3 * Hs * Ws].view(B, 3, Hs, Ws)
-        return K.jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=canvas, workspace=self._ws), sizes, labels
+        flat = self._canvas[turn][:nbytes]
+        if planes is None:
+            return K.jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=flat.view(B, 3, Hs, Ws), workspace=self._ws), sizes, labels
+        layout, _, table = planes
+        K.jpeg_reconstruct_ragged_u8(blob, descs, qtabs, table, dst=flat, workspace=self._ws, bounds=K.ragged_bounds(layout))
+        return RaggedCanvas(flat, table, layout, 3), sizes, labels

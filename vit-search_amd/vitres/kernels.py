@@ -45,7 +45,7 @@ def _p(t):
     if t is None:
         return None
     if not t.is_cuda:
-        raise RuntimeError("vitres kernels need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
+        raise RuntimeError("vitres kernels run on the GPU and need CUDA/HIP tensors (got %s); there is no CPU fallback" % t.device)
     return t.data_ptr()
 
 
@@ -913,23 +913,88 @@ def norm_constants(mean, std):
     return arr(*mean), arr(*std)
 
 
+# ---- what every wrapper of the input route does before it launches, each paragraph once ------------------------------------------------
+def _out(what, out, shape, dtype, dev, name="out"):
+    """The result tensor: a fresh one, or the caller's `name`= once it is contiguous, of that dtype and shape, on dev."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous() or out.device != dev:
+        raise ValueError("%s: %s must be a contiguous %s tensor of shape %s on %s" % (what, name, dtype, tuple(shape), dev))
+    return out
+
+
+def _upload_i32(array, dev):
+    host = torch.empty(array.shape, dtype=torch.int32, pin_memory=torch.device(dev).type == "cuda")
+    host.numpy()[...] = array
+    return host.to(dev, non_blocking=True)
+
+
+def _dev_table(what, name, table, shape, dev):
+    """A table the caller keeps on the device (and has checked): contiguous int32 of `shape` on dev; None in shape: any extent."""
+    if table.dtype != torch.int32 or table.dim() != len(shape) or any(n is not None and n != m for n, m in zip(shape, table.shape)) \
+            or not table.is_contiguous() or table.device != dev:
+        raise ValueError("%s: a device %s must be a contiguous int32 %s tensor on %s" % (
+            what, name, list("any" if n is None else n for n in shape), dev))
+    return table
+
+
+def _table(what, name, table, shape, dev, check):
+    """A device table as it is (_dev_table), a host table through check() -- the function that returns it as the int32 array the
+    device reads, or raises -- and then from pinned memory on the current stream without a host wait."""
+    if isinstance(table, torch.Tensor):
+        return _dev_table(what, name, table, shape, dev)
+    return _upload_i32(check(table), dev)
+
+
+def _u8_workspace(what, workspace, need, dev):
+    """A launch's scratch bytes: `need` of them from torch's allocator, or the caller's uint8 tensor (the entry checks its size)."""
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
+        raise ValueError("%s: the workspace is a contiguous uint8 tensor on %s" % (what, dev))
+    return workspace
+
+
+def _labels(labels, dev):
+    return labels.to(dev).long().contiguous()
+
+
+def _f32(v):
+    return float(np.float32(v))               # torch rounds python scalars to fp32
+
+
 def normalize_u8(u8, mean, std, out=None):
     """vr_normalize_u8: uint8 [B,C,H,W] -> fp32 (float(u) - mean[c] * 255) / (std[c] * 255), timm's PrefetchLoader statement bit
     for bit.  mean / std: per-channel sequences in 0..1 units, or the pair norm_constants() made of them; out: a preallocated
     contiguous fp32 tensor of the same shape."""
+    return _normalize_u8(u8, mean, std, None, out)
+
+
+def normalize_u8_erase(u8, mean, std, erase, out=None):
+    """vr_normalize_u8_erase: normalize_u8 with the erase folded into the pass -- the bits of normalize_u8 then random_erase."""
+    return _normalize_u8(u8, mean, std, erase, out)
+
+
+def _normalize_u8(u8, mean, std, erase, out):
+    what = "normalize_u8" if erase is None else "normalize_u8_erase"
     if u8.dtype != torch.uint8 or u8.dim() != 4:
-        raise TypeError("normalize_u8: a uint8 [B,C,H,W] tensor expected, got %s %s" % (u8.dtype, tuple(u8.shape)))
+        raise TypeError("%s: a uint8 [B,C,H,W] tensor expected, got %s %s" % (what, u8.dtype, tuple(u8.shape)))
     if not isinstance(mean, ctypes.Array):
         mean, std = norm_constants(mean, std)
     B, C, H, W = u8.shape
     if len(mean) != C:
-        raise ValueError("normalize_u8: %d channels but %d normalisation constants" % (C, len(mean)))
+        raise ValueError("%s: %d channels but %d normalisation constants" % (what, C, len(mean)))
+    if erase is not None:
+        check_erase_rects(erase["rects"], B, H, W, "vr_" + what)
+    _p(u8)                                                         # (a CPU tensor is refused before anything is allocated)
     u8 = u8.contiguous()
-    if out is None:
-        out = torch.empty((B, C, H, W), dtype=torch.float32, device=u8.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous():
-        raise ValueError("normalize_u8: out must be a contiguous fp32 tensor of shape %s" % ((B, C, H, W),))
-    _lib.check(_lib.lib().vr_normalize_u8(_p(u8), _p(out), B, C, H, W, mean, std, _stream()), "vr_normalize_u8")
+    out = _out(what, out, (B, C, H, W), torch.float32, u8.device)
+    args = (_p(u8), _p(out), B, C, H, W, mean, std)
+    if erase is None:
+        _lib.check(_lib.lib().vr_normalize_u8(*args, _stream()), "vr_" + what)
+    else:
+        ea, _keep = _erase_struct(erase, u8.device, "vr_" + what)
+        _lib.check(_lib.lib().vr_normalize_u8_erase(*args, ctypes.byref(ea), _stream()), "vr_" + what)
     return out
 
 
@@ -984,22 +1049,17 @@ def _mixup(x, labels, params, num_classes, on, off, norm, erase, out, targets_ou
         raise ValueError("%s: %d channels but %d normalisation constants" % (what, C, len(norm[0])))
     _p(x)                                                          # (a CPU tensor is refused before anything is allocated)
     x, dev = x.contiguous(), x.device
-    out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if out is None else out
-    targets = torch.empty((B, num_classes), dtype=torch.float32, device=dev) if targets_out is None else targets_out
-    for name, t, shape in (("out", out, (B, C, H, W)), ("targets_out", targets, (B, num_classes))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise ValueError("%s: %s must be a contiguous fp32 tensor of shape %s on %s" % (what, name, shape, dev))
-    host = torch.empty((B, MIXUP_PARAM.itemsize // 4), dtype=torch.int32, pin_memory=True)
-    host.numpy()[:] = params.view(np.int32).reshape(B, -1)
-    table = host.to(dev, non_blocking=True)
-    labels = labels.to(dev).long().contiguous()
-    args = (_p(x), _p(out), _p(labels), _p(targets), _p(table), B, C, H, W, num_classes, float(np.float32(on)), float(np.float32(off)))
+    out = _out(what, out, (B, C, H, W), torch.float32, dev)
+    targets = _out(what, targets_out, (B, num_classes), torch.float32, dev, "targets_out")
+    table = _upload_i32(params.view(np.int32).reshape(B, -1), dev)
+    labels = _labels(labels, dev)
+    args = (_p(x), _p(out), _p(labels), _p(targets), _p(table), B, C, H, W, num_classes, _f32(on), _f32(off))
     if norm is None:
         _lib.check(_lib.lib().vr_mixup(*args, _stream()), what)
     elif erase is None:
         _lib.check(_lib.lib().vr_mixup_u8(*args, norm[0], norm[1], _stream()), what)
     else:
-        ea, _table = _erase_struct(erase, dev, what)
+        ea, _keep = _erase_struct(erase, dev, what)
         _lib.check(_lib.lib().vr_mixup_u8_erase(*args, norm[0], norm[1], ctypes.byref(ea), _stream()), what)
     return out, targets
 
@@ -1038,20 +1098,13 @@ def erase_args(rects, mode, seed, call, device=None):
     return args
 
 
-def _upload_i32(array, dev):
-    host = torch.empty(array.shape, dtype=torch.int32, pin_memory=torch.device(dev).type == "cuda")
-    host.numpy()[...] = array
-    return host.to(dev, non_blocking=True)
-
-
 def _erase_struct(erase, dev, what):
     """(the vr_erase_args struct, the device table it points to -- to be kept alive until the launch is issued)"""
     rects = erase["rects"]                                                # (checked by the caller, before it allocated anything)
     table = erase.get("table")
     if table is None or table.device != dev:
         table = _upload_i32(rects, dev)
-    if table.dtype != torch.int32 or tuple(table.shape) != rects.shape or not table.is_contiguous():
-        raise ValueError("%s: the device rectangle table must be a contiguous int32 tensor of shape %s" % (what, rects.shape))
+    _dev_table(what, "rectangle table", table, rects.shape, dev)
     return _lib.EraseArgs(_p(table), rects.shape[1], ERASE_MODES[erase["mode"]], erase["seed"], erase["call"]), table
 
 
@@ -1063,64 +1116,58 @@ def random_erase(x, erase):
     B, C, H, W = x.shape
     check_erase_rects(erase["rects"], B, H, W)
     _p(x)
-    ea, _table = _erase_struct(erase, x.device, "vr_random_erase")
+    ea, _keep = _erase_struct(erase, x.device, "vr_random_erase")
     _lib.check(_lib.lib().vr_random_erase(_p(x), B, C, H, W, ea.rects, ea.R, ea.mode, ea.seed, ea.call, _stream()), "vr_random_erase")
     return x
 
 
-def normalize_u8_erase(u8, mean, std, erase, out=None):
-    """vr_normalize_u8_erase: normalize_u8 with the erase folded into the pass -- the bits of normalize_u8 then random_erase."""
-    if u8.dtype != torch.uint8 or u8.dim() != 4:
-        raise TypeError("normalize_u8_erase: a uint8 [B,C,H,W] tensor expected, got %s %s" % (u8.dtype, tuple(u8.shape)))
-    if not isinstance(mean, ctypes.Array):
-        mean, std = norm_constants(mean, std)
-    B, C, H, W = u8.shape
-    if len(mean) != C:
-        raise ValueError("normalize_u8_erase: %d channels but %d normalisation constants" % (C, len(mean)))
-    check_erase_rects(erase["rects"], B, H, W, "vr_normalize_u8_erase")
-    _p(u8)
-    u8 = u8.contiguous()
-    if out is None:
-        out = torch.empty((B, C, H, W), dtype=torch.float32, device=u8.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (B, C, H, W) or not out.is_contiguous():
-        raise ValueError("normalize_u8_erase: out must be a contiguous fp32 tensor of shape %s" % ((B, C, H, W),))
-    ea, _table = _erase_struct(erase, u8.device, "vr_normalize_u8_erase")
-    _lib.check(_lib.lib().vr_normalize_u8_erase(_p(u8), _p(out), B, C, H, W, mean, std, ctypes.byref(ea), _stream()),
-               "vr_normalize_u8_erase")
-    return out
+def token_mix(x, labels, draw, patch_len, num_classes, on, off, norm=None, erase=None, out=None, targets_out=None,
+              patch_targets_out=None):
+    """vr_token_mix (fp32 x) / vr_token_mix_u8 (uint8 x, norm = the pair norm_constants() made) / vr_token_mix_u8_erase (erase =
+    erase_args() / RandomErasing.next_args() as well): SwitchTokenMix of the batch x by `draw`
+    (vitres.token_mixup.SwitchTokenMix.draw: half, partner, the box on the patch_len grid, lam_patch, lam_img); the uint8 forms
+    normalise as normalize_u8 does, the erased one erases every sample, in normalised space, before it is mixed -- the bits of
+    normalize_u8 -> random_erase -> vr_token_mix.  on / off: the smoothed one-hot values.  Returns (out, targets, patch_targets):
+    fresh fp32 tensors, or the contiguous fp32 out= [B,C,H,W] / targets_out= [B,num_classes] / patch_targets_out=
+    [B,patch_len^2,num_classes] written in place; x is not modified."""
+    if erase is not None and norm is None:
+        raise TypeError("vr_token_mix_u8_erase normalises uint8 samples: norm = the pair norm_constants() made is required")
+    what = "vr_token_mix" if norm is None else "vr_token_mix_u8" if erase is None else "vr_token_mix_u8_erase"
+    want = torch.float32 if norm is None else torch.uint8
+    if x.dim() != 4 or x.dtype != want:
+        raise TypeError("%s: a %s [B,C,H,W] tensor expected, got %s %s" % (what, want, x.dtype, tuple(x.shape)))
+    B, C, H, W = x.shape
+    if erase is not None:
+        check_erase_rects(erase["rects"], B, H, W, what)
+    if norm is not None and len(norm[0]) != C:
+        raise ValueError("%s: input_norm has %d channels, the samples %d" % (what, len(norm[0]), C))
+    _p(x)                                                          # (a CPU tensor is refused before anything is allocated)
+    x, dev, pl = x.contiguous(), x.device, patch_len
+    out = _out(what, out, (B, C, H, W), torch.float32, dev)
+    targets = _out(what, targets_out, (B, num_classes), torch.float32, dev, "targets_out")
+    patch_targets = _out(what, patch_targets_out, (B, pl * pl, num_classes), torch.float32, dev, "patch_targets_out")
+    partner = draw["partner"].to(dev, non_blocking=True)
+    labels = _labels(labels, dev)
+    y0, y1, x0, x1 = draw["box"]
+    args = (_p(x), _p(out), _p(labels), _p(partner), _p(targets), _p(patch_targets), B, C, H, W, num_classes, pl, draw["half"], y0, y1,
+            x0, x1, _f32(draw["lam_patch"]), _f32(1. - draw["lam_patch"]), _f32(draw["lam_img"]), _f32(1. - draw["lam_img"]), _f32(on),
+            _f32(off))
+    if norm is None:
+        _lib.check(_lib.lib().vr_token_mix(*args, _stream()), what)
+    elif erase is None:
+        _lib.check(_lib.lib().vr_token_mix_u8(*args, norm[0], norm[1], _stream()), what)
+    else:
+        ea, _keep = _erase_struct(erase, dev, what)
+        _lib.check(_lib.lib().vr_token_mix_u8_erase(*args, norm[0], norm[1], ctypes.byref(ea), _stream()), what)
+    return out, targets, patch_targets
 
 
 def token_mix_u8_erase(x, labels, draw, patch_len, num_classes, on, off, norm, erase, out=None, targets_out=None,
                        patch_targets_out=None):
-    """vr_token_mix_u8_erase: SwitchTokenMix of the uint8 batch x by `draw` (vitres.token_mixup.SwitchTokenMix.draw: half, partner,
-    the box on the patch_len grid, lam_patch, lam_img) with every sample erased, in normalised space, before it is mixed -- the bits of
-    normalize_u8 -> random_erase -> vr_token_mix.  on / off: the smoothed one-hot values; norm: the pair norm_constants() made; erase:
-    erase_args() / RandomErasing.next_args().  Returns (out, targets, patch_targets): fresh fp32 tensors or the given ones."""
-    what = "vr_token_mix_u8_erase"
-    if x.dim() != 4 or x.dtype != torch.uint8:
-        raise TypeError("%s: a uint8 [B,C,H,W] tensor expected, got %s %s" % (what, x.dtype, tuple(x.shape)))
-    B, C, H, W = x.shape
-    check_erase_rects(erase["rects"], B, H, W, what)
-    _p(x)
-    x, dev, pl = x.contiguous(), x.device, patch_len
-    out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if out is None else out
-    targets = torch.empty((B, num_classes), dtype=torch.float32, device=dev) if targets_out is None else targets_out
-    patch_targets = torch.empty((B, pl * pl, num_classes), dtype=torch.float32, device=dev) if patch_targets_out is None \
-        else patch_targets_out
-    for name, t, shape in (("out", out, (B, C, H, W)), ("targets_out", targets, (B, num_classes)),
-                           ("patch_targets_out", patch_targets, (B, pl * pl, num_classes))):
-        if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise ValueError("%s must be a contiguous fp32 tensor of shape %s on %s" % (name, shape, dev))
-    partner = draw["partner"].to(dev, non_blocking=True)
-    labels = labels.to(dev).long().contiguous()
-    y0, y1, x0, x1 = draw["box"]
-    f32 = lambda v: float(np.float32(v))                                  # noqa: E731  torch rounds python scalars to fp32
-    ea, _table = _erase_struct(erase, dev, what)
-    _lib.check(_lib.lib().vr_token_mix_u8_erase(
-        _p(x), _p(out), _p(labels), _p(partner), _p(targets), _p(patch_targets), B, C, H, W, num_classes, pl, draw["half"], y0, y1, x0,
-        x1, f32(draw["lam_patch"]), f32(1. - draw["lam_patch"]), f32(draw["lam_img"]), f32(1. - draw["lam_img"]), f32(on), f32(off),
-        norm[0], norm[1], ctypes.byref(ea), _stream()), what)
-    return out, targets, patch_targets
+    """token_mix's erased form under its own name: norm and erase are required."""
+    if erase is None:
+        raise TypeError("vr_token_mix_u8_erase: erase = erase_args() / RandomErasing.next_args() is required")
+    return token_mix(x, labels, draw, patch_len, num_classes, on, off, norm, erase, out, targets_out, patch_targets_out)
 
 
 # ---- crop + resize + window + mirror of uint8 batches (vr_resample_u8; vitres/resized_crop.py draws the boxes) ---------------------------
@@ -1152,6 +1199,13 @@ def check_resample_boxes(boxes, B, Hs, Ws, out_size, what="vr_resample_u8"):
     """boxes as a contiguous int32 [B, 12] array (9 columns are padded with the reserved words) with w, h >= 1, every box inside the
     Hs x Ws canvas and every window inside its (ow, oh).  The device cannot report a bad row, so the host copy is what is checked:
     RuntimeError VR_EINVAL, before anything is launched."""
+    return _check_boxes(boxes, B, Hs, Ws, None, out_size, what, "the %d x %d canvas")
+
+
+def _check_boxes(boxes, B, rows, pitch, max_side, out_size, what, where):
+    """The box table of either route as the contiguous int32 [B, 12] array: w, h >= 1 (at most max_side, if given), every box inside
+    rows x pitch -- two ints, or one of each per sample -- and every window inside its (ow, oh).  where: how the message names
+    those limits."""
     So_h, So_w = _out_size(out_size)
     boxes = np.asarray(boxes)
     if boxes.ndim != 2 or boxes.shape[0] != B or boxes.shape[1] not in (len(RESAMPLE_BOX_FIELDS), RESAMPLE_BOX_INTS):
@@ -1159,13 +1213,17 @@ def check_resample_boxes(boxes, B, Hs, Ws, out_size, what="vr_resample_u8"):
     table = resample_boxes(B)
     table[:, :boxes.shape[1]] = boxes
     x0, y0, w, h, ow, oh, wx, wy = (table[:, i].astype(np.int64) for i in range(8))
-    bad = ((w < 1) | (h < 1) | (x0 < 0) | (y0 < 0) | (x0 + w > Ws) | (y0 + h > Hs)
+    rows, pitch = (np.broadcast_to(np.asarray(v, dtype=np.int64), (B,)) for v in (rows, pitch))
+    bad = ((w < 1) | (h < 1) | (x0 < 0) | (y0 < 0) | (x0 + w > pitch) | (y0 + h > rows)
            | (wx < 0) | (wy < 0) | (wx + So_w > ow) | (wy + So_h > oh))
+    if max_side is not None:
+        bad |= (w > max_side) | (h > max_side)
     if bad.any():
         i = int(np.flatnonzero(bad)[0])
-        raise RuntimeError("%s failed: %s: sample %d: the box x0=%d y0=%d w=%d h=%d must lie inside the %d x %d canvas and the %d x %d "
-                           "window at (%d, %d) inside the resized %d x %d image" % (what, _lib._ERR[-1], i, x0[i], y0[i], w[i], h[i], Hs,
-                                                                                    Ws, So_h, So_w, wy[i], wx[i], oh[i], ow[i]))
+        raise RuntimeError("%s failed: %s: sample %d: the box x0=%d y0=%d w=%d h=%d must lie inside %s and the %d x %d window at "
+                           "(%d, %d) inside the resized %d x %d image" % (what, _lib._ERR[-1], i, x0[i], y0[i], w[i], h[i],
+                                                                         where % (rows[i], pitch[i]), So_h, So_w, wy[i], wx[i],
+                                                                         oh[i], ow[i]))
     return table
 
 
@@ -1192,19 +1250,10 @@ def resample_u8(src, boxes, out_size, filter, out=None):
     So_h, So_w = _out_size(out_size)
     code = _resample_filter(filter)
     _p(src)
-    if isinstance(boxes, torch.Tensor):
-        if boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, RESAMPLE_BOX_INTS) or not boxes.is_contiguous() \
-                or boxes.device != src.device:
-            raise ValueError("resample_u8: a device box table must be a contiguous int32 [%d, %d] tensor on %s" % (
-                B, RESAMPLE_BOX_INTS, src.device))
-        table = boxes
-    else:
-        table = _upload_i32(check_resample_boxes(boxes, B, Hs, Ws, (So_h, So_w)), src.device)
+    table = _table("resample_u8", "box table", boxes, (B, RESAMPLE_BOX_INTS), src.device,
+                   lambda t: check_resample_boxes(t, B, Hs, Ws, (So_h, So_w)))
     src = src.contiguous()
-    if out is None:
-        out = torch.empty((B, C, So_h, So_w), dtype=torch.uint8, device=src.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, C, So_h, So_w) or not out.is_contiguous() or out.device != src.device:
-        raise ValueError("resample_u8: out must be a contiguous uint8 tensor of shape %s on %s" % ((B, C, So_h, So_w), src.device))
+    out = _out("resample_u8", out, (B, C, So_h, So_w), torch.uint8, src.device)
     _lib.check(_lib.lib().vr_resample_u8(_p(src), _p(table), _p(out), B, C, Hs, Ws, So_h, So_w, code, None, 0, _stream()),
                "vr_resample_u8")
     return out
@@ -1275,20 +1324,10 @@ def rand_augment_u8(src, table, fill, out=None):
     B, _, H, W = src.shape
     word = ra_fill(fill)
     _p(src)
-    if isinstance(table, torch.Tensor):
-        if table.dtype != torch.int32 or table.dim() != 3 or table.shape[0] != B or table.shape[2] != RA_OP_INTS \
-                or not table.is_contiguous() or table.device != src.device:
-            raise ValueError("rand_augment_u8: a device op table must be a contiguous int32 [%d, layers, %d] tensor on %s" % (
-                B, RA_OP_INTS, src.device))
-        dev_table = table
-    else:
-        dev_table = _upload_i32(check_ra_table(table, B), src.device)
+    dev_table = _table("rand_augment_u8", "op table", table, (B, None, RA_OP_INTS), src.device, lambda t: check_ra_table(t, B))
     layers = int(dev_table.shape[1])
     src = src.contiguous()
-    if out is None:
-        out = torch.empty_like(src)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(src.shape) or not out.is_contiguous() or out.device != src.device:
-        raise ValueError("rand_augment_u8: out must be a contiguous uint8 tensor of shape %s on %s" % (tuple(src.shape), src.device))
+    out = _out("rand_augment_u8", out, src.shape, torch.uint8, src.device)
     L = _lib.lib()
     need = int(L.vr_rand_augment_ws_bytes(B, H, W, layers)) if 1 <= layers <= RA_MAX_LAYERS else 0
     ws = torch.empty(need, dtype=torch.uint8, device=src.device) if need else None
@@ -1364,6 +1403,32 @@ def check_jpeg_table(descs, blob_bytes, Hs, Ws, what="vr_jpeg_reconstruct_u8"):
     return descs.view(np.int32).reshape(descs.shape[0], JPEG_DESC_INTS)
 
 
+def _qtabs(what, qtabs, B, dev):
+    """The quantisation tables [B,3,64]: uint16 bits in a 16-bit integer tensor on dev, or a host uint16 array (copied there)."""
+    if not isinstance(qtabs, torch.Tensor):
+        qtabs = np.ascontiguousarray(qtabs)
+        if qtabs.dtype != np.uint16:
+            raise TypeError("%s: host quantisation tables are uint16, got %s" % (what, qtabs.dtype))
+        qtabs = torch.from_numpy(qtabs.view(np.int16)).to(dev)
+    if qtabs.dtype not in (torch.int16, torch.uint16) or tuple(qtabs.shape) != (B, 3, 64) or not qtabs.is_contiguous() \
+            or qtabs.device != dev:
+        raise ValueError("%s: qtabs must be a contiguous 16-bit integer [%d, 3, 64] tensor on %s" % (what, B, dev))
+    return qtabs
+
+
+def _jpeg_records(what, blob, descs, Hs, Ws):
+    """The record table of either reconstruct entry on the device, and its checked host copy (None for a device table the caller
+    has checked).  Hs, Ws: the bounds the records are held to."""
+    host = None if isinstance(descs, torch.Tensor) else check_jpeg_table(descs, int(blob.numel()), Hs, Ws, "vr_" + what)
+    if host is None:
+        return _dev_table(what, "record table", descs, (None, JPEG_DESC_INTS), blob.device), None
+    return _upload_i32(host, blob.device), host
+
+
+def _jpeg_workspace(what, blob, workspace):
+    return _u8_workspace(what, workspace, int(_lib.lib().vr_jpeg_ws_bytes(int(blob.numel()))), blob.device)
+
+
 def jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=None, workspace=None):
     """vr_jpeg_reconstruct_u8: the batch's coefficient blob (uint8 device tensor, 1-D, as vitres.data.jpeg_collate lays it out) ->
     the uint8 canvas [B,3,Hs,Ws] pad_collate_u8 would have made of PIL's decoded images, bit for bit; every byte of it is written.
@@ -1371,39 +1436,17 @@ def jpeg_reconstruct_u8(blob, descs, qtabs, Hs, Ws, out=None, workspace=None):
     stream without a host wait -- or an int32 [B, 16] DEVICE tensor the caller has checked.  qtabs: the quantisation tables
     [B,3,64], uint16 bits in an int16 / uint16 tensor on the device, or a host uint16 array.  out: a preallocated canvas; workspace:
     a uint8 device tensor of at least jpeg_ws_bytes(blob.numel()) bytes (taken from torch's allocator when None)."""
-    if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
-        raise TypeError("jpeg_reconstruct_u8: the blob is a contiguous 1-D uint8 tensor, got %s %s" % (blob.dtype, tuple(blob.shape)))
+    what = "jpeg_reconstruct_u8"
+    _flat_u8(blob, what + ": blob")
     _p(blob)
-    dev, nbytes, Hs, Ws = blob.device, int(blob.numel()), int(Hs), int(Ws)
-    if isinstance(descs, torch.Tensor):
-        if descs.dtype != torch.int32 or descs.dim() != 2 or descs.shape[1] != JPEG_DESC_INTS or not descs.is_contiguous() \
-                or descs.device != dev:
-            raise ValueError("jpeg_reconstruct_u8: a device record table must be a contiguous int32 [B, %d] tensor on %s" % (
-                JPEG_DESC_INTS, dev))
-        table = descs
-    else:
-        table = _upload_i32(check_jpeg_table(descs, nbytes, Hs, Ws), dev)
+    Hs, Ws = int(Hs), int(Ws)
+    table, _host = _jpeg_records(what, blob, descs, Hs, Ws)
     B = int(table.shape[0])
-    if not isinstance(qtabs, torch.Tensor):
-        qtabs = np.ascontiguousarray(qtabs)
-        if qtabs.dtype != np.uint16:
-            raise TypeError("jpeg_reconstruct_u8: host quantisation tables are uint16, got %s" % qtabs.dtype)
-        qtabs = torch.from_numpy(qtabs.view(np.int16)).to(dev)
-    if qtabs.dtype not in (torch.int16, torch.uint16) or tuple(qtabs.shape) != (B, 3, 64) or not qtabs.is_contiguous() \
-            or qtabs.device != dev:
-        raise ValueError("jpeg_reconstruct_u8: qtabs must be a contiguous 16-bit integer [%d, 3, 64] tensor on %s" % (B, dev))
-    if out is None:
-        out = torch.empty((B, 3, Hs, Ws), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, 3, Hs, Ws) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("jpeg_reconstruct_u8: out must be a contiguous uint8 tensor of shape %s on %s" % ((B, 3, Hs, Ws), dev))
-    L = _lib.lib()
-    need = int(L.vr_jpeg_ws_bytes(nbytes))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
-        raise ValueError("jpeg_reconstruct_u8: the workspace is a contiguous uint8 tensor on %s" % (dev,))
-    _lib.check(L.vr_jpeg_reconstruct_u8(_p(blob), nbytes, _p(table), _p(qtabs), _p(out), B, Hs, Ws, _p(workspace),
-                                        int(workspace.numel()), _stream()), "vr_jpeg_reconstruct_u8")
+    qtabs = _qtabs(what, qtabs, B, blob.device)
+    out = _out(what, out, (B, 3, Hs, Ws), torch.uint8, blob.device)
+    workspace = _jpeg_workspace(what, blob, workspace)
+    _lib.check(_lib.lib().vr_jpeg_reconstruct_u8(_p(blob), int(blob.numel()), _p(table), _p(qtabs), _p(out), B, Hs, Ws, _p(workspace),
+                                                 int(workspace.numel()), _stream()), "vr_" + what)
     return out
 
 
@@ -1487,25 +1530,9 @@ def check_ragged_planes(planes, C, nbytes, sizes=None, what="vr_resample_ragged_
 def check_ragged_boxes(boxes, planes, out_size, what="vr_resample_ragged_u8"):
     """check_resample_boxes against every sample's OWN plane: w, h >= 1 (at most 8192), the box inside pitch x rows of its record,
     the window inside (ow, oh).  Returns the contiguous int32 [B, 12] table; RuntimeError VR_EINVAL for the first bad row."""
-    So_h, So_w = _out_size(out_size)
     planes = _ragged_table(planes, what)
-    B = planes.shape[0]
-    boxes = np.asarray(boxes)
-    if boxes.ndim != 2 or boxes.shape[0] != B or boxes.shape[1] not in (len(RESAMPLE_BOX_FIELDS), RESAMPLE_BOX_INTS):
-        raise ValueError("%s: the box table has shape %s, expected (%d, %d)" % (what, boxes.shape, B, RESAMPLE_BOX_INTS))
-    table = resample_boxes(B)
-    table[:, :boxes.shape[1]] = boxes
-    x0, y0, w, h, ow, oh, wx, wy = (table[:, i].astype(np.int64) for i in range(8))
-    pitch, rows = planes["pitch"].astype(np.int64), planes["rows"].astype(np.int64)
-    bad = ((w < 1) | (h < 1) | (w > RAGGED_MAX_SIDE) | (h > RAGGED_MAX_SIDE) | (x0 < 0) | (y0 < 0) | (x0 + w > pitch) | (y0 + h > rows)
-           | (wx < 0) | (wy < 0) | (wx + So_w > ow) | (wy + So_h > oh))
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise RuntimeError("%s failed: %s: sample %d: the box x0=%d y0=%d w=%d h=%d must lie inside its own %d x %d plane and the "
-                           "%d x %d window at (%d, %d) inside the resized %d x %d image" % (
-                               what, _lib._ERR[-1], i, x0[i], y0[i], w[i], h[i], rows[i], pitch[i], So_h, So_w, wy[i], wx[i], oh[i],
-                               ow[i]))
-    return table
+    return _check_boxes(boxes, planes.shape[0], planes["rows"], planes["pitch"], RAGGED_MAX_SIDE, out_size, what,
+                        "its own %d x %d plane")
 
 
 def resample_ragged_ws_bytes(C, total_rows, So_w):
@@ -1534,6 +1561,14 @@ def _flat_u8(t, what):
     return t
 
 
+def _declared_bytes(what, name, t, declared):
+    """How much of the flat buffer t a launch declares to the kernel: all of it, or the caller's figure within it."""
+    declared = int(t.numel()) if declared is None else int(declared)
+    if not 0 < declared <= t.numel():
+        raise ValueError("%s: %s_bytes must be within the %d bytes of %s" % (what, name, t.numel(), name))
+    return declared
+
+
 def jpeg_reconstruct_ragged_u8(blob, descs, qtabs, planes, dst=None, dst_bytes=None, workspace=None, bounds=None):
     """vr_jpeg_reconstruct_ragged_u8: jpeg_reconstruct_u8 into ragged planes -- every image's three planes (rows x pitch bytes each,
     zero outside the image) at its record's place in the flat uint8 buffer dst, bit for bit the bytes of the padded canvas inside
@@ -1542,64 +1577,37 @@ def jpeg_reconstruct_ragged_u8(blob, descs, qtabs, planes, dst=None, dst_bytes=N
     bounds=(Hs, Ws) >= every record's rows and pitch.  dst: None (a zeroed buffer just large enough is made) or a flat uint8 device
     tensor, of which dst_bytes (default: all) are declared to the kernel.  descs, qtabs, workspace: as jpeg_reconstruct_u8.
     Returns dst."""
-    _flat_u8(blob, "jpeg_reconstruct_ragged_u8: blob")
+    what = "jpeg_reconstruct_ragged_u8"
+    _flat_u8(blob, what + ": blob")
     _p(blob)
-    dev, nbytes = blob.device, int(blob.numel())
-    host_planes = None if isinstance(planes, torch.Tensor) else _ragged_table(planes, "vr_jpeg_reconstruct_ragged_u8")
+    dev = blob.device
+    host_planes = None if isinstance(planes, torch.Tensor) else _ragged_table(planes, "vr_" + what)
     if dst is None:
         if host_planes is None:
-            raise ValueError("jpeg_reconstruct_ragged_u8: with a device plane table the destination must be given")
+            raise ValueError("%s: with a device plane table the destination must be given" % what)
         end = (host_planes["off"].astype(np.int64) + 3 * host_planes["rows"].astype(np.int64) * host_planes["pitch"]).max()
         dst = torch.zeros(max(int(end), 1), dtype=torch.uint8, device=dev)
-    _flat_u8(dst, "jpeg_reconstruct_ragged_u8: dst")
+    _flat_u8(dst, what + ": dst")
     if dst.device != dev:
-        raise ValueError("jpeg_reconstruct_ragged_u8: dst must be on %s" % (dev,))
-    dst_bytes = int(dst.numel()) if dst_bytes is None else int(dst_bytes)
-    if not 0 < dst_bytes <= dst.numel():
-        raise ValueError("jpeg_reconstruct_ragged_u8: dst_bytes must be within the %d bytes of dst" % dst.numel())
-    if host_planes is not None:
-        Hs, Ws = ragged_bounds(host_planes) if bounds is None else (int(v) for v in bounds)
-    elif bounds is None:
-        raise ValueError("jpeg_reconstruct_ragged_u8: a device plane table needs bounds=(Hs, Ws)")
-    else:
-        Hs, Ws = (int(v) for v in bounds)
-    if isinstance(descs, torch.Tensor):
-        if descs.dtype != torch.int32 or descs.dim() != 2 or descs.shape[1] != JPEG_DESC_INTS or not descs.is_contiguous() \
-                or descs.device != dev:
-            raise ValueError("jpeg_reconstruct_ragged_u8: a device record table must be a contiguous int32 [B, %d] tensor on %s" % (
-                JPEG_DESC_INTS, dev))
-        table, sizes = descs, None
-    else:
-        host_descs = check_jpeg_table(descs, nbytes, max(Hs, 1), max(Ws, 1), "vr_jpeg_reconstruct_ragged_u8")
-        table = _upload_i32(host_descs, dev)
-        sizes = host_descs[:, [2, 1]]                                        # (height, width)
+        raise ValueError("%s: dst must be on %s" % (what, dev))
+    dst_bytes = _declared_bytes(what, "dst", dst, dst_bytes)
+    if bounds is None and host_planes is None:
+        raise ValueError("%s: a device plane table needs bounds=(Hs, Ws)" % what)
+    Hs, Ws = ragged_bounds(host_planes) if bounds is None else (int(v) for v in bounds)
+    table, host_descs = _jpeg_records(what, blob, descs, max(Hs, 1), max(Ws, 1))
     B = int(table.shape[0])
-    if host_planes is not None:
-        if host_planes.shape[0] != B:
-            raise ValueError("jpeg_reconstruct_ragged_u8: %d plane records for %d images" % (host_planes.shape[0], B))
-        ptable = _upload_i32(check_ragged_planes(host_planes, 3, dst_bytes, sizes, "vr_jpeg_reconstruct_ragged_u8"), dev)
+    if host_planes is None:
+        ptable = _dev_table(what, "plane table", planes, (B, RAGGED_PLANE_INTS), dev)
     else:
-        if planes.dtype != torch.int32 or tuple(planes.shape) != (B, RAGGED_PLANE_INTS) or not planes.is_contiguous() \
-                or planes.device != dev:
-            raise ValueError("jpeg_reconstruct_ragged_u8: a device plane table must be a contiguous int32 [%d, %d] tensor on %s" % (
-                B, RAGGED_PLANE_INTS, dev))
-        ptable = planes
-    if not isinstance(qtabs, torch.Tensor):
-        qtabs = np.ascontiguousarray(qtabs)
-        if qtabs.dtype != np.uint16:
-            raise TypeError("jpeg_reconstruct_ragged_u8: host quantisation tables are uint16, got %s" % qtabs.dtype)
-        qtabs = torch.from_numpy(qtabs.view(np.int16)).to(dev)
-    if qtabs.dtype not in (torch.int16, torch.uint16) or tuple(qtabs.shape) != (B, 3, 64) or not qtabs.is_contiguous() \
-            or qtabs.device != dev:
-        raise ValueError("jpeg_reconstruct_ragged_u8: qtabs must be a contiguous 16-bit integer [%d, 3, 64] tensor on %s" % (B, dev))
-    L = _lib.lib()
-    need = int(L.vr_jpeg_ws_bytes(nbytes))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
-        raise ValueError("jpeg_reconstruct_ragged_u8: the workspace is a contiguous uint8 tensor on %s" % (dev,))
-    _lib.check(L.vr_jpeg_reconstruct_ragged_u8(_p(blob), nbytes, _p(table), _p(qtabs), _p(dst), dst_bytes, _p(ptable), B, Hs, Ws,
-                                               _p(workspace), int(workspace.numel()), _stream()), "vr_jpeg_reconstruct_ragged_u8")
+        if host_planes.shape[0] != B:
+            raise ValueError("%s: %d plane records for %d images" % (what, host_planes.shape[0], B))
+        sizes = None if host_descs is None else host_descs[:, [2, 1]]           # (height, width)
+        ptable = _upload_i32(check_ragged_planes(host_planes, 3, dst_bytes, sizes, "vr_" + what), dev)
+    qtabs = _qtabs(what, qtabs, B, dev)
+    workspace = _jpeg_workspace(what, blob, workspace)
+    _lib.check(_lib.lib().vr_jpeg_reconstruct_ragged_u8(_p(blob), int(blob.numel()), _p(table), _p(qtabs), _p(dst), dst_bytes,
+                                                        _p(ptable), B, Hs, Ws, _p(workspace), int(workspace.numel()), _stream()),
+               "vr_" + what)
     return dst
 
 
@@ -1613,47 +1621,36 @@ def resample_ragged_u8(src, planes, boxes, C, out_size, filter, out=None, worksp
     launch; then workspace and bounds=(Hs, Ws) >= every record's rows and pitch must be given.  Host and device tables do not mix.
     workspace: a uint8 device tensor (None: taken from torch's allocator; a host-table call raises ValueError if a given one is too
     small); src_bytes: how much of src is declared to the kernel (default: all)."""
-    _flat_u8(src, "resample_ragged_u8: src")
+    what = "resample_ragged_u8"
+    _flat_u8(src, what + ": src")
     _p(src)
     dev, C = src.device, int(C)
     So_h, So_w = _out_size(out_size)
     code = _resample_filter(filter)
-    src_bytes = int(src.numel()) if src_bytes is None else int(src_bytes)
-    if not 0 < src_bytes <= src.numel():
-        raise ValueError("resample_ragged_u8: src_bytes must be within the %d bytes of src" % src.numel())
+    src_bytes = _declared_bytes(what, "src", src, src_bytes)
     if isinstance(planes, torch.Tensor) != isinstance(boxes, torch.Tensor):
-        raise ValueError("resample_ragged_u8: planes and boxes are both host tables or both device tensors")
-    L = _lib.lib()
+        raise ValueError("%s: planes and boxes are both host tables or both device tensors" % what)
     if isinstance(planes, torch.Tensor):
-        B = int(planes.shape[0])
-        if planes.dtype != torch.int32 or planes.dim() != 2 or planes.shape[1] != RAGGED_PLANE_INTS or not planes.is_contiguous() \
-                or planes.device != dev or boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, RESAMPLE_BOX_INTS) \
-                or not boxes.is_contiguous() or boxes.device != dev:
-            raise ValueError("resample_ragged_u8: device tables must be contiguous int32 [B, %d] and [B, %d] tensors on %s" % (
-                RAGGED_PLANE_INTS, RESAMPLE_BOX_INTS, dev))
+        ptable = _dev_table(what, "plane table", planes, (None, RAGGED_PLANE_INTS), dev)
+        B = int(ptable.shape[0])
+        btable = _dev_table(what, "box table", boxes, (B, RESAMPLE_BOX_INTS), dev)
         if workspace is None or bounds is None:
-            raise ValueError("resample_ragged_u8: device tables need workspace= and bounds=(Hs, Ws)")
-        Hs, Ws = (int(v) for v in bounds)
-        ptable, btable = planes, boxes
+            raise ValueError("%s: device tables need workspace= and bounds=(Hs, Ws)" % what)
+        (Hs, Ws), need = (int(v) for v in bounds), 0
     else:
-        host = _ragged_table(planes, "vr_resample_ragged_u8").copy()
+        # (not _table: the plane table is uploaded only after the boxes' heights have laid the intermediates out in it)
+        host = _ragged_table(planes, "vr_" + what).copy()
         B = host.shape[0]
-        check_ragged_planes(host, C, src_bytes, None, "vr_resample_ragged_u8")
+        check_ragged_planes(host, C, src_bytes, None, "vr_" + what)
         hb = check_ragged_boxes(boxes, host, (So_h, So_w))
         need = ragged_ws_offsets(host, C, So_w, hb[:, 3]) if 1 <= C <= 4 and So_w > 0 else 16
         Hs, Ws = ragged_bounds(host) if bounds is None else (int(v) for v in bounds)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        elif isinstance(workspace, torch.Tensor) and workspace.numel() < need:
-            raise ValueError("resample_ragged_u8: the workspace has %d bytes, the batch needs %d" % (workspace.numel(), need))
+        if isinstance(workspace, torch.Tensor) and workspace.numel() < need:
+            raise ValueError("%s: the workspace has %d bytes, the batch needs %d" % (what, workspace.numel(), need))
         ptable = _upload_i32(host.view(np.int32).reshape(B, RAGGED_PLANE_INTS), dev)
         btable = _upload_i32(hb, dev)
-    if workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.device != dev:
-        raise ValueError("resample_ragged_u8: the workspace is a contiguous uint8 tensor on %s" % (dev,))
-    if out is None:
-        out = torch.empty((B, C, So_h, So_w), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, C, So_h, So_w) or not out.is_contiguous() or out.device != dev:
-        raise ValueError("resample_ragged_u8: out must be a contiguous uint8 tensor of shape %s on %s" % ((B, C, So_h, So_w), dev))
-    _lib.check(L.vr_resample_ragged_u8(_p(src), src_bytes, _p(ptable), _p(btable), _p(out), B, C, Hs, Ws, So_h, So_w, code,
-                                       _p(workspace), int(workspace.numel()), _stream()), "vr_resample_ragged_u8")
+    workspace = _u8_workspace(what, workspace, need, dev)
+    out = _out(what, out, (B, C, So_h, So_w), torch.uint8, dev)
+    _lib.check(_lib.lib().vr_resample_ragged_u8(_p(src), src_bytes, _p(ptable), _p(btable), _p(out), B, C, Hs, Ws, So_h, So_w, code,
+                                                _p(workspace), int(workspace.numel()), _stream()), "vr_" + what)
     return out

@@ -19,8 +19,8 @@ The table of a call is left in `last_erase`; `draw=` replays it when the draw ca
 import numpy as np
 import torch
 
-from . import _lib, kernels
-from .kernels import _p, _stream, norm_constants
+from . import kernels
+from .kernels import norm_constants
 from .mixup import erase_of
 
 
@@ -82,41 +82,12 @@ class SwitchTokenMix:
         if self.input_norm is None:                               # fp32: erase a copy, then the mix as it is
             x = kernels.random_erase(samples.float().clone(memory_format=torch.contiguous_format), ea)
             return self._mix(x, targets, out, d, targets_out, patch_targets_out)
-        if len(self.input_norm[0]) != C:
-            raise ValueError('input_norm has %d channels, the samples %d' % (len(self.input_norm[0]), C))
-        off = self.smoothing / self.num_classes
-        res = kernels.token_mix_u8_erase(samples, targets, d, self.patch_len, self.num_classes, 1. - self.smoothing + off, off,
-                                         self.input_norm, ea, out=out, targets_out=targets_out, patch_targets_out=patch_targets_out)
-        return res + ('seq',)
+        return self._mix(samples, targets, out, d, targets_out, patch_targets_out, ea)
 
-    def _mix(self, samples, targets, out, draw, targets_out, patch_targets_out):
-        if not samples.is_cuda:
-            raise RuntimeError('vitres.token_mixup runs on the GPU through libvitres_hip.so (CPU restatement: oracle/)')
-        B, C, H, W = samples.shape
-        d = draw or self.draw(B)
-        K, pl = self.num_classes, self.patch_len
-        x = samples.contiguous() if self.input_norm is not None else samples.contiguous().float()
-        dev = x.device
-        out = torch.empty((B, C, H, W), dtype=torch.float32, device=dev) if out is None else out
-        new_targets = torch.empty((B, K), dtype=torch.float32, device=dev) if targets_out is None else targets_out
-        patch_targets = torch.empty((B, pl * pl, K), dtype=torch.float32, device=dev) if patch_targets_out is None \
-            else patch_targets_out
-        for name, t, shape in (('out', out, (B, C, H, W)), ('targets_out', new_targets, (B, K)),
-                               ('patch_targets_out', patch_targets, (B, pl * pl, K))):
-            if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-                raise ValueError('%s must be a contiguous fp32 tensor of shape %s on %s' % (name, shape, dev))
-        partner = d["partner"].to(dev, non_blocking=True)
-        labels = targets.to(dev).long().contiguous()
-        off = self.smoothing / K
-        on = 1. - self.smoothing + off
-        y0, y1, x0, x1 = d["box"]
-        f32 = lambda v: float(np.float32(v))                              # noqa: E731  torch rounds python scalars to fp32
-        args = (_p(x), _p(out), _p(labels), _p(partner), _p(new_targets), _p(patch_targets), B, C, H, W, K, pl, d["half"], y0, y1,
-                x0, x1, f32(d["lam_patch"]), f32(1. - d["lam_patch"]), f32(d["lam_img"]), f32(1. - d["lam_img"]), f32(on), f32(off))
-        if self.input_norm is not None:
-            if len(self.input_norm[0]) != C:
-                raise ValueError('input_norm has %d channels, the samples %d' % (len(self.input_norm[0]), C))
-            _lib.check(_lib.lib().vr_token_mix_u8(*args, self.input_norm[0], self.input_norm[1], _stream()), "vr_token_mix_u8")
-        else:
-            _lib.check(_lib.lib().vr_token_mix(*args, _stream()), "vr_token_mix")
-        return out, new_targets, patch_targets, 'seq'
+    def _mix(self, samples, targets, out, draw, targets_out, patch_targets_out, erase=None):
+        d = draw or self.draw(samples.shape[0])
+        off = self.smoothing / self.num_classes
+        x = samples if self.input_norm is not None else samples.float()
+        res = kernels.token_mix(x, targets, d, self.patch_len, self.num_classes, 1. - self.smoothing + off, off, self.input_norm, erase,
+                                out=out, targets_out=targets_out, patch_targets_out=patch_targets_out)
+        return res + ('seq',)
